@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the UNAST adversarial train step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
       N > 1 is launched by the driver as torch.distributed.run (one rank per GPU, RCCL); per-GPU batch is fixed (weak scaling).
 
 One "step" = one iteration of the reference's hot loop with ae_steps = sp_steps = d_steps = 1, cm_steps = 0
@@ -11,9 +11,13 @@ active; synthetic LJSpeech-shaped full-length batch (B=32, T_text=180, T_mel=800
 transformer_d_trans architecture (L=4, d=256, 4 heads, FFN 1024, 2-layer bi-LSTM discriminator).
 value = B * T_mel * n_gpus / step-time  [mel-frames/s].
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (dominant kernel, HIP events recorded
-inside the timed region on the launch stream) and `cpu_baseline` (the pinned oracle timed on the host cores on a bounded
-sample of the same workload; rank 0, N=1 only).
+Prints ONE JSON line (rank 0) with the driver's contract keys.  A plain run does only what that line needs: set-up, warm-up, the
+timed steps, the dump of --dump-outputs.  --full adds `roofline` (dominant kernel, HIP events on the launch stream in isolated
+single-stream steps after the timed region) and `cpu_baseline` (the pinned oracle timed on the host cores on a bounded sample of
+the same workload; rank 0, N=1 only).
+
+--dump-outputs DIR writes what the timed path computed in its last step (see dump_outputs) as DIR/<name>.npy; the inputs (weights,
+batch, dropout / noise streams) are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -187,6 +191,26 @@ def make_batch(B, Tt, Tm, seed):
     return tuple(torch.from_numpy(x) for x in synth_batch(B, Tt, Tm, seed=seed, ragged=False))
 
 
+DUMP_STATE_SAMPLE = 1 << 22         # float32 elements of the model state --dump-outputs writes (16 MB; config 3's state holds 17.3 M)
+
+
+def dump_outputs(out_dir, last_losses, state):
+    """What a caller of the train step holds after the last timed step: its losses, one loss_<name>.npy each (float64, shape [1]), and the
+    model's state (state_dict(): parameters after the optimizer update, BatchNorm running statistics) as state_sample.npy: the
+    floating-point entries flattened in key order into one float32 vector, of which a fixed sample (numpy default_rng(0), at most
+    DUMP_STATE_SAMPLE elements, ascending indices) is kept."""
+    import re
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in last_losses.items():
+        np.save(os.path.join(out_dir, "loss_%s.npy" % re.sub(r"[^A-Za-z0-9_.-]", "_", k)), np.array([v], dtype=np.float64))
+    flat = torch.cat([t.detach().reshape(-1).float() for t in state.values() if t.is_floating_point()])
+    if flat.numel() > DUMP_STATE_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_STATE_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "state_sample.npy"), flat.cpu().numpy())
+
+
 def cpu_baseline_worker(Tt, Tm, L, use_disc, Bs, budget_s):
     """Oracle (CPU restatement, pinned against the reference's golden vectors) timed on the host cores: full gen+disc steps
     (same step definition, same batch size as the GPU run): 1 warm-up + up to 3 timed steps, as many as fit the time budget."""
@@ -263,7 +287,15 @@ def main():
     ap.add_argument("--backend", default=os.environ.get("UNAST_DIST_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI) is the product path; gloo only rehearses the multi-rank logic on a 1-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline (isolated single-stream "
+                    "steps after the timed region) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's losses and a fixed sample of the model "
+                    "state as DIR/<name>.npy (dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (a.iso_detail or a.time_every) and not a.full:
+        ap.error("--iso-detail and --time-every report inside `roofline`: add --full")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -393,25 +425,84 @@ def main():
     sync()
     last = {k: float(v[-1]) for k, v in losses.items()}
     finite = all(v == v and abs(v) < 1e30 for v in last.values())
-    # Isolated launch durations: extra steps AFTER the timed region, launched kernel by kernel with everything on ONE stream and a
-    # HIP-event pair around every GEMM / attention launch on that stream (every rank runs them: the step contains the collectives).
-    # These are what `roofline` reports and what the rocprofv3 summaries in profiles/ show (average duration per kernel).
-    side = config.SIDE_STREAMS
-    config.SIDE_STREAMS = False
-    try:
-        with OpTimer(ops, ["gemm", "wgrad_group", "panel_gemm", "linear_dgrad_lnbwd", "attn_fwd", "attn_bwd"]) as ot_iso:
-            for i in range(a.iso_steps):
-                train.train_step(losses, model, opt, sched, batches, n_prime + a.warmup + a.steps + i, args)
-            sync()
-        iso = ot_iso.summary()
-    finally:
-        config.SIDE_STREAMS = side
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, model.state_dict())
+    if a.full:
+        # Isolated launch durations: extra steps AFTER the timed region, launched kernel by kernel with everything on ONE stream and a
+        # HIP-event pair around every GEMM / attention launch on that stream (every rank runs them: the step contains the collectives).
+        # These are what `roofline` reports and what the rocprofv3 summaries in profiles/ show (average duration per kernel).
+        side = config.SIDE_STREAMS
+        config.SIDE_STREAMS = False
+        try:
+            with OpTimer(ops, ["gemm", "wgrad_group", "panel_gemm", "linear_dgrad_lnbwd", "attn_fwd", "attn_bwd"]) as ot_iso:
+                for i in range(a.iso_steps):
+                    train.train_step(losses, model, opt, sched, batches, n_prime + a.warmup + a.steps + i, args)
+                sync()
+            iso = ot_iso.summary()
+        finally:
+            config.SIDE_STREAMS = side
     if dist_on:
         import torch.distributed as dist
         dist.destroy_process_group()
     if rank != 0:
         return
-    summ = ot.summary()
+    out = {"metric": "mel-frames/sec/node (train step, gen+disc) at B=32,T_mel=800; 1/2/4/8-GPU scaling",
+           "value": round(value, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+           "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "bf16x3" if config.NSPLIT == 3 else "bf16", "data": "synthetic",
+           "dist_backend": (a.backend if dist_on else None),
+           "gradient_exchange": (None if not dist_on else ("RCCL through the C ABI (unast_comm_*), issued by the stream-replay executor / ddp.py" if native else "torch.distributed all_reduce")),
+           "launch_mode": (("hip-graph replay of the captured step (unast_amd.graphed), %d untimed priming calls" % n_prime) if stepper is not None
+                           else "eager (one Python launch per kernel)" + ("; gradient buckets all-reduced during the backward (unast_amd.ddp)" if dist_on else ""))
+                          + ((" [" + auto_note + "]") if auto_note else ""),
+           "config": {"workload": "%s: %s train step (AE+SP+clip/AdamW%s), per-GPU B=%d, T_text=%d, T_mel=%d, "
+                                  "num_layers=%d, d=256, 4 heads, FFN 1024%s, dropout/noise/SpecAugment active%s" % (
+                                      a.workload, "full adversarial gen+disc" if use_disc else "generator-only", ", D step+clip/AdamW" if use_disc else "", B, Tt, Tm, L,
+                                      ", 2x bi-LSTM(64) discriminator" if use_disc else "",
+                                      (" + %d cross-model sub-step(s) with K/V-cached generation (NOT the headline configuration)" % a.cm_steps) if a.cm_steps else ""),
+                      "global_batch": B * world, "parallelism": "dp%d" % world,
+                      "precision": "split-bf16 (hi/lo) MFMA operands, fp32 accumulate and fp32 activations" if config.NSPLIT == 3 else "bf16 MFMA operands, fp32 accumulate"},
+           "graph_replay": (dict(next(iter(stepper.graphs.values())).plan_info,
+                                 **{k: v for k, v in stepper.cache_report()["per_capture"][0].items() if k in ("capture_ms", "replays", "replay_host_ms", "eager_host_ms")})
+                            if (stepper is not None and stepper.graphs) else None),
+           "host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 3),
+           "losses_finite": finite, "last_losses": {k: round(v, 5) for k, v in last.items()}}
+    if a.full:
+        out["roofline"] = roofline_report(a, ot.summary(), iso, in_region, n_timed)
+    if a.workload in STEP_TFLOP and not a.cm_steps:
+        tf = STEP_TFLOP[a.workload] * world / (ms * 1e-3)
+        out["whole_step"] = {"algorithmic_tflop_per_step_per_gpu": STEP_TFLOP[a.workload], "achieved_tflops": round(tf, 1),
+                             "frac_of_2500_dense_bf16_per_gpu": round(tf / world / PEAK_MFMA_BF16_TFLOPS, 4),
+                             "note": "SURVEY.md section 8(d) table: multiply-add = 2, backward = 2x forward, causal self-attention at T(T+1)/2"}
+    if a.full and world == 1 and not a.no_cpu_baseline:
+        try:
+            out["cpu_baseline"] = cpu_baseline(B, Tt, Tm, L, use_disc, a.cpu_budget)
+        except Exception as e:  # the checker must never take the bench down
+            out["cpu_baseline"] = {"error": repr(e)}
+    if a.profile_ops and n_timed:
+        summ = ot.summary()
+        prof = {n: round(sum(v[1] for v in summ[n].values()) / n_timed, 3) for n in summ}
+        sys.stderr.write("per-op ms/step: " + json.dumps(dict(sorted(prof.items(), key=lambda kv: -kv[1]))) + "\n")
+        for n in ("gemm", "attn_fwd", "attn_bwd"):
+            rows = sorted(summ[n].items(), key=lambda kv: -kv[1][1])[:12]
+            for k, v in rows:
+                fl = (gemm_flops(k) if n == "gemm" else attn_flops(n, k))
+                sys.stderr.write("  %-9s %-28s calls/step %5.1f  avg %8.1f us  %7.1f TF/s\n" % (n, k, v[0] / n_timed, v[1] * 1e3 / v[0], fl * v[0] / (v[1] * 1e-3) / 1e12))
+    if a.iso_detail:
+        steps_iso = max(a.iso_steps, 1)
+        for n in ("gemm", "wgrad_group", "attn_fwd", "attn_bwd"):
+            rows = sorted(iso[n].items(), key=lambda kv: -kv[1][1])[:16]
+            for k, v in rows:
+                fl = (gemm_flops(k) if n == "gemm" else group_flops(k) if n == "wgrad_group" else attn_flops(n, k))
+                sys.stderr.write("  iso %-9s %-44s calls/step %5.1f  avg %8.1f us  total %7.3f ms/step  %7.1f TF/s\n" % (
+                    n, k, v[0] / steps_iso, v[1] * 1e3 / v[0], v[1] / steps_iso, fl * v[0] / (v[1] * 1e-3) / 1e12))
+    print(json.dumps(out))
+
+
+def roofline_report(a, summ, iso, in_region, n_timed):
+    """`roofline` of the --full line: the GEMM family's HBM rate and the attention launches' MFMA rate in the isolated single-stream steps
+    (`iso`), with the committed PMC traffic and rocprofv3 averages from profiles/; `summ` = in-region event pairs (--time-every)."""
+    from unast_amd import config
 
     def family(su, n):
         calls = sum(v[0] for v in su[n].values())
@@ -493,54 +584,7 @@ def main():
         roofline["overlapped_streams"] = {"families_ms_per_step": {n: round(fr[n]["ms"] / n_timed, 3) for n in fr}, "timed_steps": n_timed,
                                           "gemm_avg_launch_us": round(fr["gemm"]["ms"] * 1e3 / max(fr["gemm"]["calls"], 1), 2),
                                           "note": "event pairs inside the timed region (eager form only): durations include time shared with other streams"}
-    out = {"metric": "mel-frames/sec/node (train step, gen+disc) at B=32,T_mel=800; 1/2/4/8-GPU scaling",
-           "value": round(value, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-           "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "bf16x3" if config.NSPLIT == 3 else "bf16", "data": "synthetic",
-           "dist_backend": (a.backend if dist_on else None),
-           "gradient_exchange": (None if not dist_on else ("RCCL through the C ABI (unast_comm_*), issued by the stream-replay executor / ddp.py" if native else "torch.distributed all_reduce")),
-           "launch_mode": (("hip-graph replay of the captured step (unast_amd.graphed), %d untimed priming calls" % n_prime) if stepper is not None
-                           else "eager (one Python launch per kernel)" + ("; gradient buckets all-reduced during the backward (unast_amd.ddp)" if dist_on else ""))
-                          + ((" [" + auto_note + "]") if auto_note else ""),
-           "config": {"workload": "%s: %s train step (AE+SP+clip/AdamW%s), per-GPU B=%d, T_text=%d, T_mel=%d, "
-                                  "num_layers=%d, d=256, 4 heads, FFN 1024%s, dropout/noise/SpecAugment active%s" % (
-                                      a.workload, "full adversarial gen+disc" if use_disc else "generator-only", ", D step+clip/AdamW" if use_disc else "", B, Tt, Tm, L,
-                                      ", 2x bi-LSTM(64) discriminator" if use_disc else "",
-                                      (" + %d cross-model sub-step(s) with K/V-cached generation (NOT the headline configuration)" % a.cm_steps) if a.cm_steps else ""),
-                      "global_batch": B * world, "parallelism": "dp%d" % world,
-                      "precision": "split-bf16 (hi/lo) MFMA operands, fp32 accumulate and fp32 activations" if config.NSPLIT == 3 else "bf16 MFMA operands, fp32 accumulate"},
-           "graph_replay": (dict(next(iter(stepper.graphs.values())).plan_info,
-                                 **{k: v for k, v in stepper.cache_report()["per_capture"][0].items() if k in ("capture_ms", "replays", "replay_host_ms", "eager_host_ms")})
-                            if (stepper is not None and stepper.graphs) else None),
-           "host_enqueue_ms_per_step": round(t_host / a.steps * 1e3, 3),
-           "losses_finite": finite, "last_losses": {k: round(v, 5) for k, v in last.items()},
-           "roofline": roofline}
-    if a.workload in STEP_TFLOP and not a.cm_steps:
-        tf = STEP_TFLOP[a.workload] * world / (ms * 1e-3)
-        out["whole_step"] = {"algorithmic_tflop_per_step_per_gpu": STEP_TFLOP[a.workload], "achieved_tflops": round(tf, 1),
-                             "frac_of_2500_dense_bf16_per_gpu": round(tf / world / PEAK_MFMA_BF16_TFLOPS, 4),
-                             "note": "SURVEY.md section 8(d) table: multiply-add = 2, backward = 2x forward, causal self-attention at T(T+1)/2"}
-    if world == 1 and not a.no_cpu_baseline:
-        try:
-            out["cpu_baseline"] = cpu_baseline(B, Tt, Tm, L, use_disc, a.cpu_budget)
-        except Exception as e:  # the checker must never take the bench down
-            out["cpu_baseline"] = {"error": repr(e)}
-    if a.profile_ops and n_timed:
-        prof = {n: round(sum(v[1] for v in summ[n].values()) / n_timed, 3) for n in summ}
-        sys.stderr.write("per-op ms/step: " + json.dumps(dict(sorted(prof.items(), key=lambda kv: -kv[1]))) + "\n")
-        for n in ("gemm", "attn_fwd", "attn_bwd"):
-            rows = sorted(summ[n].items(), key=lambda kv: -kv[1][1])[:12]
-            for k, v in rows:
-                fl = (gemm_flops(k) if n == "gemm" else attn_flops(n, k))
-                sys.stderr.write("  %-9s %-28s calls/step %5.1f  avg %8.1f us  %7.1f TF/s\n" % (n, k, v[0] / n_timed, v[1] * 1e3 / v[0], fl * v[0] / (v[1] * 1e-3) / 1e12))
-    if a.iso_detail:
-        for n in ("gemm", "wgrad_group", "attn_fwd", "attn_bwd"):
-            rows = sorted(iso[n].items(), key=lambda kv: -kv[1][1])[:16]
-            for k, v in rows:
-                fl = (gemm_flops(k) if n == "gemm" else group_flops(k) if n == "wgrad_group" else attn_flops(n, k))
-                sys.stderr.write("  iso %-9s %-44s calls/step %5.1f  avg %8.1f us  total %7.3f ms/step  %7.1f TF/s\n" % (
-                    n, k, v[0] / steps_iso, v[1] * 1e3 / v[0], v[1] / steps_iso, fl * v[0] / (v[1] * 1e-3) / 1e12))
-    print(json.dumps(out))
+    return roofline
 
 
 if __name__ == "__main__":

@@ -337,3 +337,24 @@ def test_parity_mode_and_fixed_summation_order_are_separate_switches():
     finally:
         config.DETERMINISTIC_SUMS = before
         utils.set_deterministic(False)
+
+
+def test_bench_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): one float64 file per loss, and a sample of the floating-point state entries (key order) that is
+    the same on every call, ascending, within DUMP_STATE_SAMPLE, with integer entries (BatchNorm step counters) left out."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_STATE_SAMPLE", 1000)
+    state = {"a.weight": torch.arange(3000, dtype=torch.float32).view(30, 100), "bn.num_batches_tracked": torch.tensor(7),
+             "b.weight": torch.arange(3000, 5000, dtype=torch.float32).view(100, 20).t()}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"t_ae": 1.25, "asr_": 2.5}, state)
+    assert sorted(os.listdir(tmp_path / "x")) == ["loss_asr_.npy", "loss_t_ae.npy", "state_sample.npy"]
+    assert np.load(tmp_path / "x" / "loss_t_ae.npy").tolist() == [1.25] and np.load(tmp_path / "x" / "loss_t_ae.npy").dtype == np.float64
+    s, s2 = np.load(tmp_path / "x" / "state_sample.npy"), np.load(tmp_path / "y" / "state_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (1000,) and np.array_equal(s, s2)
+    flat = np.concatenate([np.arange(3000), np.arange(3000, 5000).reshape(100, 20).T.reshape(-1)]).astype(np.float32)
+    idx = np.sort(np.random.default_rng(0).choice(5000, 1000, replace=False))
+    assert np.array_equal(s, flat[idx])
+    monkeypatch.setattr(bench, "DUMP_STATE_SAMPLE", 1 << 22)
+    bench.dump_outputs(str(tmp_path / "z"), {}, state)
+    assert np.array_equal(np.load(tmp_path / "z" / "state_sample.npy"), flat)          # small states are written whole

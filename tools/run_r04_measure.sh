@@ -8,13 +8,13 @@ mkdir -p $O
 set -x
 if [ "$pass" = "A" ]; then
   timeout -k 10 400 python -m pytest tests -m gpu -q > $O/tests.log 2>&1; echo "pytest rc=$?" >> $O/tests.log; tail -3 $O/tests.log
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-  timeout -k 10 200 python bench.py --workload c2 --no-cpu-baseline > $O/c2.json 2> $O/c2.err
-  timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --steps 10 --warmup 3 > $O/c5.json 2> $O/c5.err
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout -k 10 200 python bench.py --full --workload c2 --no-cpu-baseline > $O/c2.json 2> $O/c2.err
+  timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --steps 10 --warmup 3 > $O/c5.json 2> $O/c5.err
   grep -o "\"ms_per_step\": [0-9.]*, \"higher" $O/*.json
   cd /tmp; export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_a -- python3 $R/bench.py --launch eager --no-cpu-baseline --steps 10 --warmup 3 > $O/prof_a.log 2>&1
-  UNAST_SIDE_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b -- python3 $R/bench.py --launch eager --no-cpu-baseline --steps 6 --warmup 2 > $O/prof_b.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_a -- python3 $R/bench.py --full --launch eager --no-cpu-baseline --steps 10 --warmup 3 > $O/prof_a.log 2>&1
+  UNAST_SIDE_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b -- python3 $R/bench.py --full --launch eager --no-cpu-baseline --steps 6 --warmup 2 > $O/prof_b.log 2>&1
   cd $R
 else
   cd /tmp; export TMPDIR=/tmp

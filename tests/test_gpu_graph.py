@@ -126,6 +126,35 @@ def test_fixed_summation_order_makes_runs_agree_to_the_bit(use_disc, monkeypatch
     assert worst == 0.0 and torch.equal(pa, pc), ("eager vs replayed", worst, float((pa - pc).abs().max()))
 
 
+def test_fixed_sums_switched_on_after_a_capture_are_not_served_by_it():
+    """A capture replays the kernels chosen while it was recorded, so its key covers every setting of unast_amd.config (config.snapshot):
+    after utils.set_deterministic(True, fixed_sums=True) the next call must not replay the capture made with the atomic kernels, and
+    the stepper ends with one capture per mode."""
+    from unast_amd import utils
+    from unast_amd.graphed import GraphedTrainStep
+    was = utils.is_deterministic()
+    utils.set_deterministic(True, fixed_sums=False)
+    try:
+        args, model, opt, sched = build(2, 1e-7)
+        stepper = GraphedTrainStep(model, opt, None, args)
+        losses = defaultdict(list)
+        for i in range(3):                  # eager generator phase, eager shifted body, capture + first replay
+            stepper(losses, batches_for(i), i)
+        assert stepper.stats["replays"] == 1, stepper.stats
+        utils.set_deterministic(True, fixed_sums=True)
+        stepper(losses, batches_for(3), 3)
+        assert stepper.stats["replays"] == 1, ("the capture made with the atomic kernels was replayed under fixed sums", stepper.stats)
+        for i in (4, 5):
+            stepper(losses, batches_for(i), i)
+        assert len(stepper.graphs) == 2, stepper.stats
+        assert {dict(sig[2][2])["DETERMINISTIC_SUMS"] for sig in stepper.graphs} == {False, True}
+        stepper.flush(losses)
+        torch.cuda.synchronize()
+        assert all(np.isfinite([float(x) for x in v]).all() for v in losses.values())
+    finally:
+        utils.set_deterministic(was, fixed_sums=False)
+
+
 def test_graph_replays_draw_fresh_masks_and_permutations():
     """With the RNG sites on, replays of ONE captured graph on the SAME batch give different losses (dropout / noise /
     SpecAugment masks and the discriminator's row permutation follow the RNG epoch in device memory), all finite, and the

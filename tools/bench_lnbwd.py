@@ -2,7 +2,7 @@
 of the speech side (rows = 2 x 32 x 800 paired, contraction 1024 = FFN linear1, 768 = self-attention in-projection).  HIP events, interleaved."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from unast_amd import config, ops
+from unast_amd import ops
 from unast_amd.planes import Planes
 D = torch.device("cuda:0")
 
@@ -26,7 +26,6 @@ for M in (51200, 25600):
         ops._weight_planes = lambda w, transposed=False: pl.ref(0) if transposed else None
         dx = torch.empty(M, E, device=D); dz = torch.empty(M, E, device=D); dzd = torch.empty(M, E, device=D)
         dg = torch.zeros(E, device=D); db = torch.zeros(E, device=D)
-        config.LN_FINALIZE_OFFLOAD = False
         a = lambda: ops.linear_dgrad(dy, W, dx, R=R)
         b = lambda: ops.layernorm_bwd(dx, z, gamma, mean, rstd, dz, dzd, dg, db, drop_p=0.1, seed=3, stream_id=2)
         c = lambda: ops.linear_dgrad_lnbwd(dy, W, R, z, mean, rstd, gamma, dz, dzd, dg, db, drop_p=0.1, seed=3, stream_id=2)

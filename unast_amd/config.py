@@ -15,9 +15,11 @@ def precision_name():
     return "bf16" if NSPLIT == 1 else "bf16x3"
 
 
-# Weights as GEMM B operands are read from a pre-split copy kept next to the flat parameter store (engine.FlatStore);
-# off = the kernels re-split the fp32 weights in every row panel (bit-identical results; for A/B timing only).
-PRESPLIT_WEIGHTS = os.environ.get("UNAST_PRESPLIT", "1") != "0"
+def snapshot():
+    """Every setting of this module as a sorted tuple of (name, value): part of the key of a captured train step
+    (graphed.GraphedTrainStep), so that a capture is never replayed under settings other than those it was recorded with."""
+    return tuple(sorted((k, v) for k, v in globals().items() if k.isupper()))
+
 
 # Inside the train-step functions the text side, the speech side and the discriminator run on three HIP streams (their
 # launches under-fill the chip one at a time); 0 = everything on the caller's stream.  Direct calls of model methods outside
@@ -28,27 +30,12 @@ SIDE_STREAMS = os.environ.get("UNAST_SIDE_STREAMS", "1") != "0"
 # host launch overhead); 0 = launch every kernel from Python.
 DECODE_GRAPH = os.environ.get("UNAST_DECODE_GRAPH", "1") != "0"
 
-# Weight-gradient GEMMs (and their split-K reductions) are issued on a companion stream of the side stream they come from:
-# they are off the backward pass's critical chain (their results are read by the optimizer only) and bandwidth-bound, while
-# the chain they leave behind is attention / dgrad work.  Needs SIDE_STREAMS.
-WGRAD_STREAMS = os.environ.get("UNAST_WGRAD_STREAMS", "1") != "0"
-# ... only for weight gradients that reduce over at least this many tokens: the hand-off costs ~15 us of host time per launch,
-# which small (launch-bound) configurations cannot hide (config 2: 22.7 -> 27.7 ms/step without this gate).
+# The speech side's weight-gradient GEMMs (and their split-K reductions, and the reductions of LayerNorm's gamma / beta gradient
+# partials) are issued on a companion stream (engine.side_streams): they are off the backward pass's critical chain (their results
+# are read by the optimizer only) and bandwidth-bound, while the chain they leave behind is attention / dgrad work.  Only those that
+# reduce over at least this many tokens: the hand-off costs ~15 us of host time per launch, which small (launch-bound)
+# configurations cannot hide (config 2: 22.7 -> 27.7 ms/step without this gate).
 WGRAD_STREAM_MIN_TOKENS = int(os.environ.get("UNAST_WGRAD_MIN_TOKENS", "8192"))
-# Only the speech side gets a companion: text + speech + discriminator + speech companion = exactly four real streams, one per
-# hardware queue of HIP's default (see unast_amd/__init__.py); the text side's weight gradients are small and the
-# discriminator's run fine on its own stream (same-box A/B: 37.9 ms/step either way, tools/stream_groups_ab.sh).
-WGRAD_COMPANION_OF = set(x for x in os.environ.get("UNAST_WGRAD_COMPANION_OF", "speech").split(",") if x)
-# The reduction of LayerNorm's gamma / beta gradient partials is off the backward chain too (same companion stream, same gate).
-LN_FINALIZE_OFFLOAD = os.environ.get("UNAST_LN_FINALIZE_INLINE", "0") != "1"
-
-# Which logical streams share a real HIP stream ("a:x,b:x" puts a and b on the stream named x).  Experiment switch.
-STREAM_GROUPS = dict(kv.split(":") for kv in os.environ.get("UNAST_STREAM_GROUPS", "").split(",") if ":" in kv)
-
-# HIP stream priority per logical stream ("speech:-1,text:0"; lower = more urgent, as in torch.cuda.Stream(priority=)): the step's critical
-# chain is the speech side; what runs beside it on the other streams takes CUs from its kernels.  The stream replay creates its streams
-# with the priorities of the streams the nodes were captured on (csrc/graph_exec.cpp).
-STREAM_PRIORITY = {k: int(v) for k, v in (kv.split(":") for kv in os.environ.get("UNAST_STREAM_PRIO", "").split(",") if ":" in kv)}
 
 # Fixed summation order of every fp32 sum (ops.deterministic_sums; utils.set_deterministic(True, fixed_sums=True) sets it).
 DETERMINISTIC_SUMS = os.environ.get("UNAST_DETERMINISTIC_SUMS", "0") == "1"
@@ -56,10 +43,6 @@ DETERMINISTIC_SUMS = os.environ.get("UNAST_DETERMINISTIC_SUMS", "0") == "1"
 # While a HIP graph is being captured, a backward segment drops the dependencies its stream inherited from the origin stream's relay that
 # are not the producers of its own incoming gradients (engine._Segment._backward; include/unast_hip.h unast_capture_prune).  0 = round-2 form.
 CAPTURE_PRUNE = os.environ.get("UNAST_CAPTURE_PRUNE", "1") != "0"
-
-# LayerNorm backward in the epilogue of the input-gradient GEMM that produces its dy (ops.linear_dgrad_lnbwd; inside the encoder / decoder
-# stacks, where a sub-layer's output has the next sub-layer as its only consumer).  0 = GEMM + stand-alone LayerNorm backward.
-PANEL_LNBWD = os.environ.get("UNAST_PANEL_LNBWD", "1") != "0"
 
 # Weight gradients of one backward closure (an attention sub-layer's out-proj + in-proj, an FFN's two linears, ...) go out as
 # ONE grouped launch (csrc/gemm.hip gemm_group_kernel) instead of one split-K launch + one reduction each; 0 = one by one.
@@ -80,30 +63,14 @@ ATTN_BWD_TERMS = int(os.environ.get("UNAST_ATTN_BWD_TERMS", "3"))
 # it is OFF by default (it costs a second 68 MB weight copy and a refresh launch per optimizer phase); 1 = on.
 DGRAD_TRANSPOSED = os.environ.get("UNAST_DGRAD_T", "0") == "1"
 
-# The in-projections write Q / K / V -- and the out-projection's input-gradient GEMM writes dO -- in the pre-split operand format;
-# the attention kernels then stage K/V (forward) and Q/dO (backward) tiles without fp32 -> hi/lo conversions.  0 = fp32 (A/B).
-ATTN_PRESPLIT = os.environ.get("UNAST_ATTN_PRESPLIT", "1") != "0"
-
-# BatchNorm batch statistics of the conv stacks taken in the conv GEMM's epilogue (unast_gemm colstats) instead of by a column-sum
-# pass over the conv output.  0 = the separate pass (A/B).
-CONV_BN_STATS = os.environ.get("UNAST_CONV_BN_STATS", "1") != "0"
-
-# Row-panel GEMM (csrc/panel.hip) for K <= 256 contractions over at least PANEL_MIN_ROWS rows: the activation panel stays in registers,
-# the weights stream through LDS by LDS-DMA from tiled bf16 planes kept next to the flat parameter store (engine.FlatStore).  Measured on
-# MI355X against the tile GEMM at M = 25 600 (tools/bench_panel.py): linear1 51-54 vs 67-70 us, in-projection 42-45 vs 47-52, out-projection
-# 17.6 vs 21, K/V projection 29 vs 36, prenet fc1 11 vs 14.7; at M = 5 760 (text side) the tile kernel is faster.  0 = tile GEMM everywhere.
-PANEL_GEMM = os.environ.get("UNAST_PANEL", "1") != "0"
+# Row-panel GEMM (csrc/panel.hip) for K <= 256 contractions -- and, K-streamed, K > 256 contractions into 256 columns -- over at least
+# PANEL_MIN_ROWS rows: the activation panel stays in registers, the weights stream through LDS by LDS-DMA from tiled bf16 planes kept next to
+# the flat parameter store (engine.FlatStore).  Measured on MI355X against the tile GEMM at M = 25 600 (tools/bench_panel.py): linear1 51-54 vs
+# 67-70 us, in-projection 42-45 vs 47-52, out-projection 17.6 vs 21, K/V projection 29 vs 36, prenet fc1 11 vs 14.7; at M = 5 760 (text side)
+# the tile kernel is faster.
 PANEL_MIN_ROWS = int(os.environ.get("UNAST_PANEL_MIN_ROWS", "16384"))
 # 1128 = 128-row panels as 16 waves x 16 rows (4 waves / SIMD); 128 = 8 waves x 32 rows; 64 = 8 waves x 16 rows
 PANEL_ROWS = int(os.environ.get("UNAST_PANEL_ROWS", "1128"))
-# LayerNorm in the epilogue of the out-projection GEMMs (post-LN sub-layers): z, y, mean, rstd come out of one launch.
-PANEL_LN = os.environ.get("UNAST_PANEL_LN", "1") != "0"
-# K > 256 contractions into 256 columns (FFN linear2 with its LayerNorm, the input gradients of linear1 / the in-projections) on the
-# K-streamed form of the panel kernel
-PANEL_KSTREAM = os.environ.get("UNAST_PANEL_KSTREAM", "1") != "0"
-# linear1 writes one keep bit per hidden element (relu > 0 and not dropped); linear2's input-gradient GEMM gates with those bits
-# (scalar loads) instead of re-reading the 105 MB hidden activation.
-PANEL_GATE_BITS = os.environ.get("UNAST_PANEL_GATE_BITS", "1") != "0"
 
 # Data-parallel gradient exchange through the C ABI's own RCCL communicator (csrc/comm.cpp: unast_comm_init / unast_allreduce) instead of
 # torch.distributed calls: stream-ordered, one ctypes call per bucket, and -- because the stream-replay executor can issue it from C++ --
@@ -126,14 +93,6 @@ DEBUG_WORKSPACES = os.environ.get("UNAST_DEBUG_WORKSPACES", "0") == "1"
 
 # The generator phase of an outer step with one auto-encoder and one supervised sub-step (ae_steps = sp_steps = 1, no cross-model sub-step,
 # both batches in one shape) as ONE forward and ONE backward (train.train_gen_joint_step): each encoder's stack runs once over both
-# sub-steps' batches, the frozen discriminator once over both sub-steps' encoder outputs.  0 = the two sub-steps one after the other.
+# sub-steps' batches, each decoder once over both sub-steps' targets, the frozen discriminator once over both sub-steps' encoder outputs.
+# 0 = the two sub-steps one after the other.
 JOINT_GEN = os.environ.get("UNAST_JOINT_GEN", "1") != "0"
-
-# Heads and losses in one launch each (north_star): the text head's GEMM computes the cross-entropy and its gradient from its accumulators
-# (csrc/loss.hip text_head_loss_kernel) when the step tells the decoder call what the loss will be (decode_sequence(..., loss_hint=));
-# text_loss() then only hands the results over.  0 = head GEMM, loss forward and loss backward as three launches.
-FUSED_HEAD_LOSS = os.environ.get("UNAST_FUSED_HEAD_LOSS", "1") != "0"
-
-# ... and the two speech decoder calls of the joint generator step as one (SpeechTransformer.decode_pair): self-attention and feed-forward
-# over both sub-steps' targets, cross-attention per call.  0 = two decode_sequence calls.
-JOINT_DECODERS = os.environ.get("UNAST_JOINT_DECODERS", "1") != "0"

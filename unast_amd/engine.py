@@ -30,18 +30,11 @@ class _Streams:
     trace = None         # list of (stream name, call, start event, end event) when tracing
 
 
-def _stream_group(name):
-    """Logical stream name -> the real stream it runs on (several logical streams may share one)."""
-    from . import config
-    return config.STREAM_GROUPS.get(name, name)
-
-
 def _side(name):
-    key = (torch.cuda.current_device(), _stream_group(name))
+    key = (torch.cuda.current_device(), name)
     s = _Streams.pool.get(key)
     if s is None:
-        from . import config
-        s = _Streams.pool[key] = torch.cuda.Stream(priority=config.STREAM_PRIORITY.get(key[1], 0))
+        s = _Streams.pool[key] = torch.cuda.Stream()
     return s
 
 
@@ -68,8 +61,7 @@ class side_streams:
         if self.active:
             _Streams.enabled = True
             _Streams.producer.clear()
-            if config.WGRAD_STREAMS:
-                ops.WGRAD_SIDE = _wgrad_stream_of_current
+            ops.WGRAD_SIDE = _wgrad_stream_of_current
         return self
 
     def __exit__(self, *exc):
@@ -82,15 +74,15 @@ class side_streams:
 
 
 def _wgrad_stream_of_current():
-    """Companion stream "<name>_w" of the side stream that is current (None on any other stream)."""
-    cur = torch.cuda.current_stream()
-    dev = torch.cuda.current_device()
-    from . import config
-    for (d, name), s in _Streams.pool.items():
-        if d == dev and s == cur and name in config.WGRAD_COMPANION_OF:
-            _Streams.used.add(name + "_w")
-            return _side(name + "_w")
-    return None
+    """Companion stream "speech_w" when the speech side's stream is current (None on any other stream).  Only the speech side gets one:
+    text + speech + discriminator + speech companion = exactly four real streams, one per hardware queue of HIP's default (see
+    unast_amd/__init__.py); the text side's weight gradients are small and the discriminator's run fine on its own stream (DESIGN.md
+    section 1)."""
+    s = _Streams.pool.get((torch.cuda.current_device(), "speech"))
+    if s is None or s != torch.cuda.current_stream():
+        return None
+    _Streams.used.add("speech_w")
+    return _side("speech_w")
 
 
 def join_wgrad_streams():
@@ -173,10 +165,6 @@ def wait(waiter, source_stream, event=None):
         waiter.wait_stream(source_stream)
 
 
-import os as _os
-_FORCE_VIA_ORIGIN = _os.environ.get("UNAST_VIA_ORIGIN", "0") == "1"      # experiment: the capture-time hand-off discipline in eager mode
-
-
 class _ViaOrigin(torch.autograd.Function):
     """Identity placed -- on the CALLER's stream -- on an edge between two side streams while a HIP graph is being captured.
     ROCm 7.2's hipStreamEndCapture crashes when a side stream waits on an event of another side stream that has itself waited
@@ -233,7 +221,7 @@ def on_stream(name):
             s = _side(name)
             if cur == s:
                 return fn(*args, **kw)
-            via_origin = torch.cuda.is_current_stream_capturing() or _FORCE_VIA_ORIGIN
+            via_origin = torch.cuda.is_current_stream_capturing()
             waited = set()
             inputs = set()
             cross = set()
@@ -567,10 +555,8 @@ class FlatStore:
         of W^T (the operand of its input-gradient GEMM dX = dY W); combined operands (the [81, 256] head, the LSTM's [2 * 4H, Din]
         input projections) and the q rows of the cross-attention in-projections likewise.  `refresh_planes` re-tiles a region with
         one launch (unast_retile_weights) after every optimizer step and whenever sync_split() sees parameters written through torch."""
-        from . import config, planes
+        from . import planes
         self._pmats, self._pcache, self.planes_buf, self._pdescs = [], {}, None, {}
-        if not config.PANEL_GEMM:
-            return
         cands = []                                   # (flat offset, source row stride, rows, cols, region)
         for n, p in self.params.items():
             if p.dim() == 2 and not n.endswith(".conv.weight"):

@@ -106,20 +106,19 @@ def attn_sublayer(cx, tape, x, mem, lens_k, causal, pre_attn, pre_norm, B, Tq, T
     s_attn, s_out = cx.stream(), cx.stream()
     # Q / K / V (and dO below) are read by the attention kernels only: the projections store them pre-split (hi/lo bf16 chunks), so
     # the K/V tiles every query block stages -- and Q / dO in the backward -- need no fp32 -> hi/lo conversion there
-    ps = config.ATTN_PRESPLIT
     if mem is None:
         qkv = _empty(Nq, 3 * E, like=x.v)
-        ops.linear_fwd(x.v, W, bias, qkv, out_split=ps)
+        ops.linear_fwd(x.v, W, bias, qkv, out_split=True)
         Q, K, V = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
     else:
         q = _empty(Nq, E, like=x.v)
         kv = _empty(Nk, 2 * E, like=x.v)
-        ops.linear_fwd(x.v, W[:E], bias[:E], q, out_split=ps)
-        ops.linear_fwd(mem.v, W[E:], bias[E:], kv, out_split=ps)
+        ops.linear_fwd(x.v, W[:E], bias[:E], q, out_split=True)
+        ops.linear_fwd(mem.v, W[E:], bias[E:], kv, out_split=True)
         Q, K, V = q, kv[:, :E], kv[:, E:]
     O = _empty(Nq, E, like=x.v)
     LSE = _empty(B, H, Tq, like=x.v)
-    ops.attn_fwd(Q, K, V, O, LSE, lens_k, B, H, Tq, Tk, causal, drop_p=p, seed=cx.seed, stream_id=s_attn, qkv_split=ps)
+    ops.attn_fwd(Q, K, V, O, LSE, lens_k, B, H, Tq, Tk, causal, drop_p=p, seed=cx.seed, stream_id=s_attn, qkv_split=True)
     z = _empty(Nq, E, like=x.v)
     y, mean, rstd = _empty(Nq, E, like=x.v), _empty(Nq, like=x.v), _empty(Nq, like=x.v)
     # z = x + drop(O Wo^T + bo), y = LayerNorm(z): one launch where the row-panel GEMM serves the shape, GEMM + LayerNorm otherwise
@@ -143,13 +142,13 @@ def attn_sublayer(cx, tape, x, mem, lens_k, causal, pre_attn, pre_norm, B, Tq, T
             if gWo is not None:
                 ops.linear_wgrad(da, O, gWo, db=st.g(pre_attn + "out_proj.bias"))
             dO = _empty(Nq, E, like=z)
-            ops.linear_dgrad(da, Wo, dO, out_split=ps)
+            ops.linear_dgrad(da, Wo, dO, out_split=True)
             delta = _empty(B, H, Tq, like=z)
             gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
             if mem is None:
                 dqkv = _empty(Nq, 3 * E, like=z)
                 ops.attn_bwd(Q, K, V, O, dO, LSE, delta, dqkv[:, :E], dqkv[:, E:2 * E], dqkv[:, 2 * E:], lens_k, B, H, Tq, Tk, causal,
-                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=ps, lens_q=lens_k if (pad_free_grads and config.ENC_SKIP_PAD_GRADS) else None)
+                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=True, lens_q=lens_k if (pad_free_grads and config.ENC_SKIP_PAD_GRADS) else None)
                 if gW is not None:
                     ops.linear_wgrad(dqkv, x.v, gW, db=gb)
                 _input_grad(cx, x, dqkv, W, dz)
@@ -157,7 +156,7 @@ def attn_sublayer(cx, tape, x, mem, lens_k, causal, pre_attn, pre_norm, B, Tq, T
                 dq = _empty(Nq, E, like=z)
                 dkv = _empty(Nk, 2 * E, like=z)
                 ops.attn_bwd(Q, K, V, O, dO, LSE, delta, dq, dkv[:, :E], dkv[:, E:], lens_k, B, H, Tq, Tk, causal,
-                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=ps)
+                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=True)
                 if gW is not None:
                     ops.linear_wgrad(dq, x.v, gW[:E], db=gb[:E])
                     ops.linear_wgrad(dkv, mem.v, gW[E:], db=gb[E:])
@@ -181,19 +180,18 @@ def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_nor
     Wo, bo = cx.P[pre_attn + "out_proj.weight"], cx.P[pre_attn + "out_proj.bias"]
     p = cx.p(drop)
     s_attn, s_out = (cx.stream(), cx.stream()), cx.stream()
-    ps = config.ATTN_PRESPLIT
     q2 = _empty(2 * N, E, like=x2.v)
-    ops.linear_fwd(x2.v, W[:E], bias[:E], q2, out_split=ps)
+    ops.linear_fwd(x2.v, W[:E], bias[:E], q2, out_split=True)
     kvs = []
     for h in range(2):
         kv = _empty(B * Tks[h], 2 * E, like=x2.v)
-        ops.linear_fwd(mems[h].v, W[E:], bias[E:], kv, out_split=ps)
+        ops.linear_fwd(mems[h].v, W[E:], bias[E:], kv, out_split=True)
         kvs.append(kv)
     O2 = _empty(2 * N, E, like=x2.v)
     LSE2 = _empty(2, B, H, Tq, like=x2.v)
     for h in range(2):
         ops.attn_fwd(q2[h * N:(h + 1) * N], kvs[h][:, :E], kvs[h][:, E:], O2[h * N:(h + 1) * N], LSE2[h], lens_ks[h], B, H, Tq, Tks[h], False,
-                     drop_p=p, seed=cx.seed, stream_id=s_attn[h], qkv_split=ps)
+                     drop_p=p, seed=cx.seed, stream_id=s_attn[h], qkv_split=True)
     z = _empty(2 * N, E, like=x2.v)
     y, mean, rstd = _empty(2 * N, E, like=x2.v), _empty(2 * N, like=x2.v), _empty(2 * N, like=x2.v)
     ops.linear_fwd(O2, Wo, bo, z, drop_p=p, seed=cx.seed, stream_id=s_out, R=x2.v, ln=(cx.P[pre_norm + "weight"], cx.P[pre_norm + "bias"], y, mean, rstd, LN_EPS))
@@ -213,7 +211,7 @@ def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_nor
                 if gWo is not None:
                     ops.linear_wgrad(da, O2, gWo, db=st.g(pre_attn + "out_proj.bias"))
                 dO = _empty(2 * N, E, like=z)
-                ops.linear_dgrad(da, Wo, dO, out_split=ps)
+                ops.linear_dgrad(da, Wo, dO, out_split=True)
                 gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
                 dq2 = _empty(2 * N, E, like=z)
                 dkvs = []
@@ -222,7 +220,7 @@ def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_nor
                     dkv = _empty(B * Tks[h], 2 * E, like=z)
                     ops.attn_bwd(q2[h * N:(h + 1) * N], kvs[h][:, :E], kvs[h][:, E:], O2[h * N:(h + 1) * N], dO[h * N:(h + 1) * N], LSE2[h], delta,
                                  dq2[h * N:(h + 1) * N], dkv[:, :E], dkv[:, E:], lens_ks[h], B, H, Tq, Tks[h], False,
-                                 drop_p=p, seed=seed, stream_id=s_attn[h], qkv_split=ps)
+                                 drop_p=p, seed=seed, stream_id=s_attn[h], qkv_split=True)
                     dkvs.append(dkv)
                     dmem = _empty(B * Tks[h], E, like=z)
                     ops.linear_dgrad(dkv, W[E:], dmem)
@@ -298,7 +296,7 @@ def ffn_sublayer(cx, tape, x, pre, pre_norm, drop):
     h = _empty(N, F, like=x.v)
     # keep bits of h (relu > 0 and not dropped) for the backward's gate, when both GEMMs that touch them run on the row-panel kernel
     bits = None
-    if tape is not None and config.PANEL_GATE_BITS and F % 64 == 0 and F <= 1024 and ops.panel_serves(N, E, W1) and ops.panel_serves(N, E, W2, transposed=True):
+    if tape is not None and F % 64 == 0 and F <= 1024 and ops.panel_serves(N, E, W1) and ops.panel_serves(N, E, W2, transposed=True):
         bits = torch.empty(ops.gate_bits_bytes(N, F), dtype=torch.uint8, device=x.v.device)
     ops.linear_fwd(x.v, W1, b1, h, act=1, drop_p=p, seed=cx.seed, stream_id=s1, gate_bits=bits)
     z = _empty(N, E, like=x.v)
@@ -408,11 +406,10 @@ def conv_bn_act(cx, tape, x, B, T, conv_pre, bn_pre, pad_left, act, drop, bn_buf
     Cout, _, Cin = Wp.shape
     x3 = x.v.view(B, T, -1)[..., :Cin] if x.v.shape[1] != Cin else x.v.view(B, T, Cin)
     c = _empty(B, T, Cout, like=x.v)
-    fused_stats = cx.training and config.CONV_BN_STATS
     # [0, 2C): sum / sum of squares per channel out of the conv GEMM's epilogue; [2C, 4C): the backward's column sums (both pre-zeroed)
     ws4 = pool.take(Cout) if (pool is not None and cx.training) else torch.zeros(4 * Cout, dtype=torch.float64, device=x.v.device)
     ws, ws_b = ws4[:2 * Cout], ws4[2 * Cout:]
-    ops.conv_fwd(x3, Wp, b, c, pad_left, colstats=ws if fused_stats else None)
+    ops.conv_fwd(x3, Wp, b, c, pad_left, colstats=ws if cx.training else None)
     p = cx.p(drop)
     s = cx.stream()
     N = B * T
@@ -421,7 +418,7 @@ def conv_bn_act(cx, tape, x, B, T, conv_pre, bn_pre, pad_left, act, drop, bn_buf
     rm, rv = bn_buffers[bn_pre + "running_mean"], bn_buffers[bn_pre + "running_var"]
     gamma, beta = cx.P[bn_pre + "weight"], cx.P[bn_pre + "bias"]
     if cx.training:
-        ops.bn_fwd(c.view(N, Cout), gamma, beta, y, mean, rstd, rm, rv, ws, act, drop_p=p, seed=cx.seed, stream_id=s, have_sums=fused_stats,
+        ops.bn_fwd(c.view(N, Cout), gamma, beta, y, mean, rstd, rm, rv, ws, act, drop_p=p, seed=cx.seed, stream_id=s, have_sums=True,
                    num_batches_tracked=bn_buffers[bn_pre + "num_batches_tracked"])
     else:
         if tape is not None:
@@ -589,7 +586,7 @@ def text_decode_tail(cx, tape, m, x, loss_hint=None, dx_out=None):
     W, b = cx.P["text_m.postnet.fc1.weight"], cx.P["text_m.postnet.fc1.bias"]
     V = W.shape[0]
     ldl = (V + 3) // 4 * 4
-    if loss_hint is not None and tape is not None and E == 256 and V <= 48 and config.FUSED_HEAD_LOSS:
+    if loss_hint is not None and tape is not None and E == 256 and V <= 48:
         # loss_hint = (gold [B, T] int64, eos_weight, gscale, loss workspace): head GEMM, cross-entropy and its gradient in one launch
         gold, eos_w, gscale, ws = loss_hint
         logits = torch.empty(N, ldl, dtype=torch.float32, device=x.v.device)
@@ -730,7 +727,7 @@ def speech_decode_tail(cx, tape, m, x, mel, postnet=True, loss_hint=None, dx_out
     bh = st.span("speech_m.postnet.linear_project.bias", "speech_m.postnet.stop_linear.bias", (M + 1,))
     ldh = (M + 1 + 3) // 4 * 4
     fused = None
-    if loss_hint is not None and tape is not None and postnet and E == 256 and M % 4 == 0 and M + 1 <= 96 and config.FUSED_HEAD_LOSS and \
+    if loss_hint is not None and tape is not None and postnet and E == 256 and M % 4 == 0 and M + 1 <= 96 and \
             Wh.data_ptr() % 16 == 0 and bh.data_ptr() % 16 == 0:
         # loss_hint = (gold mel [B, T, M], lengths int32 [B], eos_weight, gscale, loss workspace): the heads, the pre-net MSE, the stop BCE and
         # their gradient in one launch; the post-net term and the scalar follow behind the post-net (speech_post_loss below)

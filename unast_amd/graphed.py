@@ -21,7 +21,8 @@ step k ]  with the same dependencies (D update before the generator's own D call
 update after everything).  The first call runs its generator phase eagerly, `flush()` runs the last pending D phase.
 
 Variable input shapes: the captured unit reads the discriminator batch of step k-1 and the generator batches of step k, so a capture
-is keyed by BOTH shapes (and the mode flags); static input buffers are kept per shape and shared by the captures that read them.
+is keyed by BOTH shapes (and by the modes and every setting of unast_amd.config: config.snapshot); static input buffers are kept per
+shape and shared by the captures that read them.
 Captures live in an LRU (MAX_GRAPHS entries, UNAST_MAX_GRAPHS) and allocate from ONE private memory pool -- replays never overlap
 and leave nothing alive but their loss vector, so the pool holds the largest step's working set once, not once per capture.  A
 (shape, shape) pair is run eagerly the first time it is met and captured the second time (a pair met once costs nothing extra);
@@ -56,7 +57,7 @@ class _Captured:
 # launch for a nearly linear graph (config 2, no discriminator: 16 cross-stream edges, 9.7 vs 10.5 ms/step) and the slower
 # executor for a heavily forked one (config 3: 190 cross-stream edges, 35-39 vs 32 ms/step).  MI355X, ROCm 7.2.
 REPLAY = os.environ.get("UNAST_GRAPH_REPLAY", "auto")
-REPLAY_STREAMS = int(os.environ.get("UNAST_GRAPH_REPLAY_STREAMS", "4"))       # 32.2 / 34.1 / 35.1 / 35.6 ms/step with 4 / 5 / 6 / 8 at config 3
+REPLAY_STREAMS = 4       # 32.2 / 34.1 / 35.1 / 35.6 ms/step with 4 / 5 / 6 / 8 at config 3
 AUTO_MIN_CROSS_EDGES = 64
 
 
@@ -91,7 +92,7 @@ class GraphedTrainStep:
         shp = lambda k, n: tuple((k, i, tuple(tuple(t.shape) for t in batches[k][i])) for i in range(n))
         gen = shp("unsup", a.ae_steps) + shp("sup", a.sp_steps)
         disc = shp("disc", a.d_steps) if a.use_discriminator else ()
-        return gen, disc, (is_deterministic(), config.NSPLIT, self.model.training, config.JOINT_GEN, config.JOINT_DECODERS)
+        return gen, disc, (is_deterministic(), self.model.training, config.snapshot())
 
     @staticmethod
     def _static_like(batch, dev):
@@ -168,7 +169,7 @@ class GraphedTrainStep:
         model._store().sync_split()                       # parameters written through torch since the last step?
         gen_sig, disc_sig, flags = self._signatures(batches)
         if self.pending_lr is not None and flags != self.flags:
-            self.flush(losses)                            # mode change (deterministic / eval): the pending D phase belongs to the old mode
+            self.flush(losses)                            # mode or setting change (deterministic / eval / config): the pending D phase belongs to the old one
         self.flags = flags
         lr_now = float(opt.param_groups[0]["lr"])
         if a.use_discriminator and self.pending_lr is None:

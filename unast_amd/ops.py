@@ -3,6 +3,8 @@
 Every function enqueues HIP kernels on torch's current stream.  Tensors are fp32 CUDA tensors owned by torch
 (device-memory plumbing); shapes are validated here and again on the C side.
 """
+import os as _os
+
 import torch
 
 from . import config
@@ -98,7 +100,7 @@ def gemm(a_mode, b_mode, A, lda, B, ldb, C, ldc, M, N, K, conv=(0, 0, 0, 0), bia
     bp, presplit = _p(B), 0
     if b_ptr is not None:
         bp, presplit = b_ptr, 1
-    elif _WEIGHT_SPANS and config.PRESPLIT_WEIGHTS and a_mode != OP_RC:      # forward / dgrad forms: B may be a stored weight
+    elif _WEIGHT_SPANS and a_mode != OP_RC:      # forward / dgrad forms: B may be a stored weight
         sp = _presplit_ptr(bp)
         if sp:
             bp, presplit = sp, 1
@@ -108,9 +110,8 @@ def gemm(a_mode, b_mode, A, lda, B, ldb, C, ldc, M, N, K, conv=(0, 0, 0, 0), bia
                            int(out_split), _p(colstats), _stream()), "unast_gemm")
 
 
-import os as _os
-SPLITK_TARGET_BLOCKS = int(_os.environ.get("UNAST_SPLITK_TARGET", "256"))      # one workgroup per CU: 36.4 vs 36.8 ms/step at 320 (same box)
-SPLITK_MIN_KSTEPS = int(_os.environ.get("UNAST_SPLITK_MINK", "10"))
+SPLITK_TARGET_BLOCKS = 256      # one workgroup per CU: 36.4 vs 36.8 ms/step at 320 (same box)
+SPLITK_MIN_KSTEPS = 10
 
 
 def _splitk_for(M, N, K):
@@ -127,9 +128,9 @@ def _splitk_for(M, N, K):
 
 
 def _panel_ok(M, K, *tensors, N=None):
-    if not (config.PANEL_GEMM and config.NSPLIT == 3 and M >= config.PANEL_MIN_ROWS and K >= 4 and K % 4 == 0):
+    if not (config.NSPLIT == 3 and M >= config.PANEL_MIN_ROWS and K >= 4 and K % 4 == 0):
         return False
-    if K > 256 and not (config.PANEL_KSTREAM and K % 64 == 0 and N is not None and N % 256 == 0):      # the K-streamed form: 256-column output tiles
+    if K > 256 and not (K % 64 == 0 and N is not None and N % 256 == 0):      # the K-streamed form: 256-column output tiles
         return False
     for t in tensors:
         if t is not None and (t.stride(-1) != 1 or t.data_ptr() % 16 or t.stride(0) % 4):
@@ -145,7 +146,7 @@ def linear_fwd(x2d, W, bias, out, act=0, drop_p=0.0, seed=0, stream_id=0, R=None
     keep bit per output element (panel kernel only; see linear_dgrad)."""
     M, K = x2d.shape
     N = W.shape[0]
-    fuse_ln = ln is not None and config.PANEL_LN and N == 256 and not out_split and act == 0
+    fuse_ln = ln is not None and N == 256 and not out_split and act == 0
     deep = K > 256                                  # K-streamed form: plain / residual / LayerNorm epilogues (dropout inside the LayerNorm one only)
     if _panel_ok(M, K, x2d, out, R, N=N) and W.stride(1) == 1 and (R is None or fuse_ln or deep) and \
             not (deep and (act or out_split or gate_bits is not None or (drop_p > 0 and not fuse_ln))):       # (K <= 256: a residual operand is served by the LayerNorm epilogue only)
@@ -214,7 +215,7 @@ def linear_dgrad_lnbwd(dy2d, W, R, z, mean, rstd, gamma, dz, dz_drop, dgamma, db
     kernel does not serve the shape: contraction dy2d.shape[1] > 256 and a multiple of 64, 256 output columns, at least
     config.PANEL_MIN_ROWS rows, tiled planes of W^T, 16-byte operands."""
     M, N = dy2d.shape
-    if not (config.PANEL_LNBWD and W.shape[1] == 256 and N > 256 and W.stride(1) == 1 and z.shape[1] == 256 and
+    if not (W.shape[1] == 256 and N > 256 and W.stride(1) == 1 and z.shape[1] == 256 and
             _panel_ok(M, N, dy2d, dz, R, z, dz_drop, N=256) and gamma.data_ptr() % 16 == 0):
         return False
     wp = _weight_planes(W, transposed=True)
@@ -233,7 +234,7 @@ def linear_dgrad_lnbwd(dy2d, W, R, z, mean, rstd, gamma, dz, dz_drop, dgamma, db
     if dgamma is not None:      # the reduction of the parameter-gradient partials is off the backward chain: companion stream
         nblk = (M + 127) // 128
         _on_wgrad_stream(lambda: check(lib().unast_layernorm_partials_finalize(_p(part), nblk, 256, _p(dgamma), _p(dbeta), _stream()),
-                                       "unast_layernorm_partials_finalize"), M if config.LN_FINALIZE_OFFLOAD else 0, dgamma.data_ptr(), part)
+                                       "unast_layernorm_partials_finalize"), M, dgamma.data_ptr(), part)
     return True
 
 
@@ -301,7 +302,7 @@ class _WgradItem(_ct.Structure):          # include/unast_hip.h: unast_wgrad_ite
 
 _BATCH = None            # list of pending (dy2d, x2d, dW, db) while inside `wgrad_batch()`
 GROUP_MAX = 8
-WGRAD_GROUP_TARGET = int(_os.environ.get("UNAST_WGRAD_GROUP_TARGET", "256"))      # workgroups per grouped launch: 29.42 vs 29.65 ms/step at 512 (three alternating runs each, same box; round 2 preferred 512 when one stream bounded the step)
+WGRAD_GROUP_TARGET = 256      # workgroups per grouped launch: 29.42 vs 29.65 ms/step at 512 (three alternating runs each, same box; round 2 preferred 512 when one stream bounded the step)
 
 
 class wgrad_batch:
@@ -512,7 +513,7 @@ def layernorm_bwd(dy, z, gamma, mean, rstd, dz, dz_drop=None, dgamma=None, dbeta
                                     rows, C, drop_p, seed & 0xFFFFFFFF, stream_id, 0 if dgamma is not None else 1, _stream()), "unast_layernorm_bwd")
     if dgamma is not None:      # the reduction of the parameter-gradient partials is off the backward chain: companion stream
         _on_wgrad_stream(lambda: check(lib().unast_layernorm_bwd_finalize(_p(ws), ws_n, rows, C, _p(dgamma), _p(dbeta), _stream()),
-                                       "unast_layernorm_bwd_finalize"), rows if config.LN_FINALIZE_OFFLOAD else 0, dgamma.data_ptr(), ws)
+                                       "unast_layernorm_bwd_finalize"), rows, dgamma.data_ptr(), ws)
 
 
 def colsum(x2d, out):

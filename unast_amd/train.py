@@ -517,10 +517,6 @@ def train_ae_step(losses, model, batch, step, accum_steps, args):
     return loss
 
 
-_JOINT_D_FIRST = os.environ.get("UNAST_JOINT_D_FIRST", "0") == "1"       # experiment switches of train_gen_joint_step
-_JOINT_D_PAIR = os.environ.get("UNAST_JOINT_D_PAIR", "1") != "0"
-
-
 class _JoinRows(torch.autograd.Function):
     """`buf` already holds the row blocks `parts` (each a view of it, written in place by its producer): returns buf as ONE tensor that
     autograd connects to every block's producer; the gradient goes back as row-block views.  (torch.cat would copy 2 x 52 MB per call.)"""
@@ -544,11 +540,14 @@ def train_gen_joint_step(losses, model, ae_batch, sp_batch, step, accum_steps, a
     optimizer_step of the generator phase, src/train.py:609-628) as ONE forward and ONE backward.  Gradients of the two sub-steps add up
     before the update in the reference too, so the joint backward of (ae losses + sp losses) / accum_steps changes no result; what it
     buys: each encoder runs its stack once over both sub-steps' batches (encode_pair: 2B sequences per launch -- the text side's
-    45-180-workgroup GEMMs double --, BatchNorm statistics / running-stat updates stay per sub-step and in the reference's order), the
-    frozen LSTM discriminator scores both sub-steps' encoder outputs in one call (4B sequences: 256 workgroups per recurrent launch
-    instead of 128, 8 launches per step instead of 12), and the two sub-steps' decoders are independent work on two streams.
-    Needs both batches in one shape; otherwise (or with config.JOINT_GEN off) the caller runs the two sub-steps one after the other."""
-    from . import config
+    45-180-workgroup GEMMs double --, BatchNorm statistics / running-stat updates stay per sub-step and in the reference's order), each
+    decoder runs once over both sub-steps' targets (decode_pair), and the frozen LSTM discriminator scores both sub-steps' encoder outputs
+    in one call (4B sequences: 256 workgroups per recurrent launch instead of 128, 8 launches per step instead of 12).
+    Needs both batches in one shape (ValueError otherwise); joint_generator_phase tells the caller whether to run the two sub-steps one
+    after the other instead."""
+    if any(tuple(a.shape) != tuple(b.shape) for a, b in zip(ae_batch[:2], sp_batch[:2])):
+        raise ValueError("train_gen_joint_step: the two batches' text / mel shapes differ: %s vs %s"
+                         % ([tuple(t.shape) for t in ae_batch[:2]], [tuple(t.shape) for t in sp_batch[:2]]))
     (xa, ya), (xs, ys) = process_batch(ae_batch), process_batch(sp_batch)
     text_a, mel_a, tl_a, ml_a = xa
     text_s, mel_s, tl_s, ml_s = xs
@@ -560,42 +559,25 @@ def train_gen_joint_step(losses, model, ae_batch, sp_batch, step, accum_steps, a
         def disc_losses():
             if not use_d:
                 return None, None
-            if _JOINT_D_PAIR:       # both sub-steps' discriminator batches side by side in one buffer, one discriminator call
-                B, Tmax, Dm = text_a.shape[0], max(text_a.shape[1], mel_a.shape[1]), t_enc_a.shape[-1]
-                with torch.cuda.stream(stream_of("disc") or torch.cuda.current_stream()):
-                    d_buf = torch.empty(4 * B, Tmax, Dm, dtype=torch.float32, device=t_enc_a.device)
-                d_a = discriminator_shuffle_batch(t_masks_a[2], tl_a, s_masks_a[2], ml_a, args.model_type, out=d_buf[:2 * B])
-                d_s = discriminator_shuffle_batch(t_masks_s[2], tl_s, s_masks_s[2], ml_s, args.model_type, out=d_buf[2 * B:])
-                return _discriminator_pair_losses(model, d_buf, d_a, d_s)
-            d_a = discriminator_shuffle_batch(t_masks_a[2], tl_a, s_masks_a[2], ml_a, args.model_type)
-            la_, _ = discriminator_hidden_to_loss(model, d_a, freeze_discriminator=True)
-            d_s = discriminator_shuffle_batch(t_masks_s[2], tl_s, s_masks_s[2], ml_s, args.model_type)
-            ls_, _ = discriminator_hidden_to_loss(model, d_s, freeze_discriminator=True)
-            return la_, ls_
-        if _JOINT_D_FIRST:
-            d_ae_loss, d_sp_loss = disc_losses()
+            # both sub-steps' discriminator batches side by side in one buffer, one discriminator call
+            B, Tmax, Dm = text_a.shape[0], max(text_a.shape[1], mel_a.shape[1]), t_enc_a.shape[-1]
+            with torch.cuda.stream(stream_of("disc") or torch.cuda.current_stream()):
+                d_buf = torch.empty(4 * B, Tmax, Dm, dtype=torch.float32, device=t_enc_a.device)
+            d_a = discriminator_shuffle_batch(t_masks_a[2], tl_a, s_masks_a[2], ml_a, args.model_type, out=d_buf[:2 * B])
+            d_s = discriminator_shuffle_batch(t_masks_s[2], tl_s, s_masks_s[2], ml_s, args.model_type, out=d_buf[2 * B:])
+            return _discriminator_pair_losses(model, d_buf, d_a, d_s)
         # the auto-encoder sub-step's decoders, then the supervised sub-step's (BatchNorm of the speech post-net: first ae, then tts)
         gs = 1.0 / float(accum_steps)          # the upstream gradient of every loss of this step (train._LossSum): the fused head + loss launches apply it
         dev = t_enc_a.device
         th_a, th_s = (ya[0], args.t_eos_weight, gs, _loss_ws(dev)), (ys[0], args.t_eos_weight, gs, _loss_ws(dev))
-        pair_text = config.JOINT_DECODERS and text_a.shape == text_s.shape
-        if pair_text:           # the auto-encoder's text decoder and the ASR decoder as one call (memories: text / speech encoder output)
-            text_pred_a, text_pred_s = (o.permute(0, 2, 1) for o in model.text_m.decode_pair(text_a, tl_a, t_enc_a, t_masks_a, th_a,
-                                                                                             text_s, tl_s, s_enc_s, s_masks_s, th_s))
-        else:
-            text_pred_a = model.text_m.decode_sequence(text_a, tl_a, t_enc_a, t_masks_a, loss_hint=th_a).permute(0, 2, 1)
+        # the auto-encoder's text decoder and the ASR decoder as one call (memories: text / speech encoder output)
+        text_pred_a, text_pred_s = (o.permute(0, 2, 1) for o in model.text_m.decode_pair(text_a, tl_a, t_enc_a, t_masks_a, th_a,
+                                                                                         text_s, tl_s, s_enc_s, s_masks_s, th_s))
         hint_a, hint_s = (ya[1], ml_a, args.s_eos_weight, gs, _loss_ws(dev)), (ys[1], ml_s, args.s_eos_weight, gs, _loss_ws(dev))
-        if config.JOINT_DECODERS and mel_a.shape == mel_s.shape:
-            # the auto-encoder's speech decoder and the TTS decoder as one call: the stack once over both, cross-attention per call
-            (pre_a, post_a, stop_a, _), (pre_s, post_s, stop_s, _) = model.speech_m.decode_pair(mel_a, ml_a, s_enc_a, s_masks_a, hint_a,
-                                                                                                 mel_s, ml_s, t_enc_s, t_masks_s, hint_s)
-        else:
-            pre_a, post_a, stop_a, _ = model.speech_m.decode_sequence(mel_a, ml_a, s_enc_a, s_masks_a, loss_hint=hint_a)
-            pre_s, post_s, stop_s, _ = model.speech_m.decode_sequence(mel_s, ml_s, t_enc_s, t_masks_s, loss_hint=hint_s)
-        if not pair_text:
-            text_pred_s = model.text_m.decode_sequence(text_s, tl_s, s_enc_s, s_masks_s, loss_hint=th_s).permute(0, 2, 1)
-        if not _JOINT_D_FIRST:
-            d_ae_loss, d_sp_loss = disc_losses()
+        # the auto-encoder's speech decoder and the TTS decoder as one call: the stack once over both, cross-attention per call
+        (pre_a, post_a, stop_a, _), (pre_s, post_s, stop_s, _) = model.speech_m.decode_pair(mel_a, ml_a, s_enc_a, s_masks_a, hint_a,
+                                                                                             mel_s, ml_s, t_enc_s, t_masks_s, hint_s)
+        d_ae_loss, d_sp_loss = disc_losses()        # after the decoders: issued before them, every later call would inherit the waits for both encoder pairs
         s_ae_loss = speech_loss(ya[1], ya[2], pre_a, post_a, ml_a, stop_a, args.s_eos_weight)
         t_ae_loss = text_loss(ya[0], text_pred_a, args.t_eos_weight)
         tts_loss = speech_loss(ys[1], ys[2], pre_s, post_s, ml_s, stop_s, args.s_eos_weight)

@@ -11,7 +11,7 @@ import torch
 
 from . import config, ops
 from .engine import Var, acc
-from .utils import is_deterministic
+from .utils import is_deterministic, lens_i32
 
 LN_EPS = 1e-5
 
@@ -521,7 +521,13 @@ def text_encode_pair(cx, tape, m, ids_a, noise_a, ids_b, noise_b, lens2):
 
 
 FUSED_STATS = {"text_head": 0, "text_grad_direct": 0, "text_grad_general": 0, "speech_head": 0, "speech_grad_direct": 0, "speech_grad_general": 0}      # launches so far (tests)
-FUSED_LOSSES = {}      # storage address of a head's output buffer -> what the fused head + loss launch left for the loss call (train.text_loss / speech_loss)
+
+
+def _hint_conforms(dev, eos_w, gscale, *tensors):
+    """Whether a loss_hint holds what the fused head + loss kernels read through raw pointers: every (tensor, dtype, elements) contiguous on
+    `dev` with that dtype and element count, eos_weight and gscale finite."""
+    return math.isfinite(float(eos_w)) and math.isfinite(float(gscale)) and all(
+        torch.is_tensor(t) and t.dtype == dt and t.device == dev and t.numel() == n and t.is_contiguous() for t, dt, n in tensors)
 
 
 def text_decode(cx, tape, m, ids, lens_q, mem, lens_k, Tk, shift=True, loss_hint=None):
@@ -586,17 +592,21 @@ def text_decode_tail(cx, tape, m, x, loss_hint=None, dx_out=None):
     W, b = cx.P["text_m.postnet.fc1.weight"], cx.P["text_m.postnet.fc1.bias"]
     V = W.shape[0]
     ldl = (V + 3) // 4 * 4
+    logits = None
     if loss_hint is not None and tape is not None and E == 256 and V <= 48:
-        # loss_hint = (gold [B, T] int64, eos_weight, gscale, loss workspace): head GEMM, cross-entropy and its gradient in one launch
+        # loss_hint = (gold [B, T] int64, eos_weight, gscale, loss workspace): head GEMM, cross-entropy and its gradient in one launch, unless
+        # the kernel could misread the hint.  The record rides on the logits buffer: train.text_loss takes it off through its input's view
+        # base, and it is freed with the buffer
         gold, eos_w, gscale, ws = loss_hint
-        logits = torch.empty(N, ldl, dtype=torch.float32, device=x.v.device)
-        dlogits = torch.empty(N, ldl, dtype=torch.float32, device=x.v.device)
-        loss = torch.empty(1, dtype=torch.float32, device=x.v.device)
         goldc = gold.contiguous().view(-1)
-        ops.text_head_loss(xd, W, b, goldc, V, eos_w, gscale, logits, dlogits, ws, loss)
-        FUSED_STATS["text_head"] += 1
-        FUSED_LOSSES[logits.untyped_storage().data_ptr()] = dict(kind="text", loss=loss, dlogits=dlogits, gold=goldc, eos_weight=float(eos_w), gscale=float(gscale), ws=ws)
-    else:
+        if _hint_conforms(x.v.device, eos_w, gscale, (goldc, torch.int64, N), (ws, torch.float64, 8)):
+            logits = torch.empty(N, ldl, dtype=torch.float32, device=x.v.device)
+            dlogits = torch.empty(N, ldl, dtype=torch.float32, device=x.v.device)
+            loss = torch.empty(1, dtype=torch.float32, device=x.v.device)
+            ops.text_head_loss(xd, W, b, goldc, V, eos_w, gscale, logits, dlogits, ws, loss)
+            FUSED_STATS["text_head"] += 1
+            logits.fused_loss = dict(kind="text", loss=loss, dlogits=dlogits, gold=goldc, eos_weight=float(eos_w), gscale=float(gscale), ws=ws)
+    if logits is None:
         logits = torch.zeros(N, ldl, dtype=torch.float32, device=x.v.device)
         ops.linear_fwd(xd, W, b, logits[:, :V])
     out = Var(logits)
@@ -729,16 +739,18 @@ def speech_decode_tail(cx, tape, m, x, mel, postnet=True, loss_hint=None, dx_out
     fused = None
     if loss_hint is not None and tape is not None and postnet and E == 256 and M % 4 == 0 and M + 1 <= 96 and \
             Wh.data_ptr() % 16 == 0 and bh.data_ptr() % 16 == 0:
-        # loss_hint = (gold mel [B, T, M], lengths int32 [B], eos_weight, gscale, loss workspace): the heads, the pre-net MSE, the stop BCE and
-        # their gradient in one launch; the post-net term and the scalar follow behind the post-net (speech_post_loss below)
+        # loss_hint = (gold mel [B, T, M] float32, lengths [B], eos_weight, gscale, loss workspace): the heads, the pre-net MSE, the stop BCE and
+        # their gradient in one launch, unless the kernel could misread the hint; the post-net term and the scalar follow behind the post-net
+        # (speech_post_loss below)
         gold, glens, eos_w, gscale, ws = loss_hint
-        goldc = gold.contiguous()
-        head = torch.empty(N, ldh, dtype=torch.float32, device=mel.device)
-        d_head = torch.empty(N, ldh, dtype=torch.float32, device=mel.device)
-        ops.speech_head_loss(x.v, Wh, bh, goldc.view(N, M), glens, B, T, M, eos_w, gscale, head, d_head, ws)
-        FUSED_STATS["speech_head"] += 1
-        fused = dict(kind="speech", gold=goldc, lens=glens, eos_weight=float(eos_w), gscale=float(gscale), ws=ws, d_head=d_head)
-    else:
+        goldc, glens = gold.contiguous(), lens_i32(glens, mel.device)
+        if _hint_conforms(mel.device, eos_w, gscale, (goldc, torch.float32, N * M), (glens, torch.int32, B), (ws, torch.float64, 8)):
+            head = torch.empty(N, ldh, dtype=torch.float32, device=mel.device)
+            d_head = torch.empty(N, ldh, dtype=torch.float32, device=mel.device)
+            ops.speech_head_loss(x.v, Wh, bh, goldc.view(N, M), glens, B, T, M, eos_w, gscale, head, d_head, ws)
+            FUSED_STATS["speech_head"] += 1
+            fused = dict(kind="speech", gold=goldc, lens=glens, eos_weight=float(eos_w), gscale=float(gscale), ws=ws, d_head=d_head)
+    if fused is None:
         head = torch.zeros(N, ldh, dtype=torch.float32, device=mel.device)
         ops.linear_fwd(x.v, Wh, bh, head[:, :M + 1])
     headv = Var(head)
@@ -777,7 +789,7 @@ def speech_decode_tail(cx, tape, m, x, mel, postnet=True, loss_hint=None, dx_out
         fused["d_post"] = torch.empty(B, T, M, dtype=torch.float32, device=mel.device)
         fused["loss"] = torch.empty(1, dtype=torch.float32, device=mel.device)
         ops.speech_post_loss(fused["gold"].view(N, M), postv.v, fused["lens"], B, T, M, fused["gscale"], fused["d_post"], fused["ws"], fused["loss"])
-        FUSED_LOSSES[head.untyped_storage().data_ptr()] = fused
+        head.fused_loss = fused                                     # for train.speech_loss, through its pred_mel's view base (see text_decode_tail)
     if tape is not None:
         def bwd_conv2():
             if postv.g is None:

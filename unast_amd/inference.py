@@ -20,6 +20,7 @@ Semantics note: with dropout active (model.train() under no_grad, as in cm_text_
 fresh masks for every prefix position at every step; the cached form draws them once per position.  With the RNG sites
 off (parity tests) and in eval mode the two are identical.
 """
+import gc
 import math
 
 import torch
@@ -113,20 +114,28 @@ def _capture(fn, pool=None, keep_graph=False):
     graph = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()      # keep_graph: the hipGraph_t stays readable
     from . import engine
     cs.wait_stream(cur)
-    with torch.cuda.stream(cs):
-        graph.capture_begin(**({"pool": pool} if pool is not None else {}))
-        engine.capture_begins(cs)            # explicit waits between forked streams are checked from here on (engine._CaptureWaits)
-        try:
-            fn()
-        except BaseException:
-            engine.capture_ends()
+    # No garbage collection inside the capture: a CUDAGraph the collector frees there (one held in a reference cycle, such as the model
+    # <-> GraphedTrainStep pair train() makes) synchronises the device in its destructor on ROCm, which fails under capture and aborts.
+    gc_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.stream(cs):
+            graph.capture_begin(**({"pool": pool} if pool is not None else {}))
+            engine.capture_begins(cs)            # explicit waits between forked streams are checked from here on (engine._CaptureWaits)
             try:
-                graph.capture_end()            # close the capture so that the stream is usable again; the error below is the one to report
-            except Exception:
-                pass
-            raise
-        engine.capture_ends()
-        graph.capture_end()
+                fn()
+            except BaseException:
+                engine.capture_ends()
+                try:
+                    graph.capture_end()            # close the capture so that the stream is usable again; the error below is the one to report
+                except Exception:
+                    pass
+                raise
+            engine.capture_ends()
+            graph.capture_end()
+    finally:
+        if gc_on:
+            gc.enable()
     cur.wait_stream(cs)
     return graph
 

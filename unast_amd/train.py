@@ -23,7 +23,7 @@ from collections import defaultdict
 import torch
 import torch.nn as nn
 
-from . import ddp, ops
+from . import ddp, functional as F, ops
 from .engine import Var, run_segment, on_stream, side_streams, join_streams, stream_of, join_wgrad_streams
 from .network import TextTransformer, SpeechTransformer, UNAST, Discriminator, LSTMDiscriminator, _as_padded
 from .utils import (PAD_IDX, SOS_IDX, EOS_IDX, lens_i32, specaugment, sent_lens_to_mask, get_teacher_ratio, is_deterministic,
@@ -200,20 +200,36 @@ def masked_mse(gold_mel, pred_mel, mel_mask):
     return ops.masked_mse(gold, pred, mask)
 
 
+def _fused_loss(pred, kind, eos_weight, gold, lens=None):
+    """The record a fused head + loss launch left on the buffer behind `pred` (functional.text_decode_tail / speech_decode_tail), taken off
+    it, when it describes this loss: same kind, eos_weight and gold shape, the same gold (and lengths) tensors by address.  Nothing here
+    reads device memory; any other loss returns None and takes the general kernels."""
+    rec = vars(pred if pred._base is None else pred._base).pop("fused_loss", None)
+    if rec is None or rec["kind"] != kind or rec["eos_weight"] != float(eos_weight) or rec["gold"].shape != gold.shape \
+            or rec["gold"].data_ptr() != gold.data_ptr() or (lens is not None and rec["lens"].data_ptr() != lens.data_ptr()):
+        return None
+    return rec
+
+
+def _fused_grad_applies(rec, g):
+    """Whether the gradient the fused launch computed is the one wanted: the upstream gradient g is a resident constant equal to the gscale
+    it was scaled by.  Counted in functional.FUSED_STATS."""
+    known = _known_value(g)
+    direct = known is not None and abs(known - rec["gscale"]) <= 1e-12 * abs(known)
+    F.FUSED_STATS[rec["kind"] + ("_grad_direct" if direct else "_grad_general")] += 1
+    return direct
+
+
 @on_stream("text")
 def text_loss(gold_char, text_pred, eos_weight=1.0):
     """src/train.py:105-111.  text_pred is [B, V, T] as in the reference call sites (logits.permute(0, 2, 1)).  When the decoder call that
     produced text_pred was told about this loss (decode_sequence(..., loss_hint=), as train_gen_joint_step does), the head GEMM has
     already computed it and its gradient (csrc/loss.hip text_head_loss_kernel); this call then launches nothing."""
     B, V, T = text_pred.shape
-    gold = gold_char.to(text_pred.device).contiguous().view(-1)
+    gold = gold_char.to(text_pred.device, torch.int64).contiguous().view(-1)
     ldl = (V + 3) // 4 * 4
     lg_btv = text_pred.permute(0, 2, 1)
-    from . import functional as F
-    fused = F.FUSED_LOSSES.pop(text_pred.untyped_storage().data_ptr(), None)
-    if fused is not None and not (fused["kind"] == "text" and fused["eos_weight"] == float(eos_weight) and fused["gold"].shape == gold.shape
-                                  and (fused["gold"].data_ptr() == gold.data_ptr() or torch.equal(fused["gold"], gold))):
-        fused = None                     # another loss than the one announced: compute it the ordinary way
+    fused = _fused_loss(text_pred, "text", eos_weight, gold)
 
     def fwd(loss):
         if fused is not None:
@@ -226,19 +242,14 @@ def text_loss(gold_char, text_pred, eos_weight=1.0):
     def bwd(g, saved):
         logits, ws = saved
         if fused is not None:
-            known = _known_value(g)
-            if known is not None and abs(known - fused["gscale"]) <= 1e-12 * abs(known):
+            if _fused_grad_applies(fused, g):
                 dl = fused["dlogits"]            # already scaled by exactly this upstream gradient
-                F.FUSED_STATS["text_grad_direct"] += 1
                 return (dl.view(B, T, ldl)[..., :V].permute(0, 2, 1),)
-            F.FUSED_STATS["text_grad_general"] += 1
             logits = _as_padded(lg_btv.detach(), B * T, ldl, V)          # another upstream gradient than announced: the general kernel
         dl = torch.empty(B * T, ldl, dtype=torch.float32, device=g.device)
         ops.text_loss_bwd(logits, gold, V, float(eos_weight), ws, g, dl)
         return (dl.view(B, T, ldl)[..., :V].permute(0, 2, 1),)
-    if fused is not None:
-        return _scalar_segment(fwd, bwd, text_pred, loss_tensor=fused["loss"])
-    return _scalar_segment(fwd, bwd, text_pred)
+    return _scalar_segment(fwd, bwd, text_pred, loss_tensor=None if fused is None else fused["loss"])
 
 
 @on_stream("speech")
@@ -246,17 +257,11 @@ def speech_loss(gold_mel, stop_label, pred_mel, post_pred_mel, mel_len, stop_pre
     """src/train.py:113-122.  stop_label is implied by mel_len (one-hot at len-1, src/train.py:88) and not read."""
     B, T, M = pred_mel.shape
     ldh = (M + 1 + 3) // 4 * 4
-    gold = gold_mel.to(pred_mel.device).contiguous()
+    gold = gold_mel.to(pred_mel.device, torch.float32).contiguous()
     lens = lens_i32(mel_len, pred_mel.device)
     if stop_pred.dim() == 3:
         stop_pred = stop_pred.squeeze(-1)
-
-    from . import functional as F
-    fused = F.FUSED_LOSSES.pop(pred_mel.untyped_storage().data_ptr(), None)
-    if fused is not None and not (fused["kind"] == "speech" and fused["eos_weight"] == float(eos_weight) and fused["gold"].shape == gold.shape
-                                  and (fused["gold"].data_ptr() == gold.data_ptr() or torch.equal(fused["gold"], gold))
-                                  and (fused["lens"].data_ptr() == lens.data_ptr() or torch.equal(fused["lens"], lens))):
-        fused = None                     # another loss than the one announced to decode_sequence(loss_hint=): the ordinary way
+    fused = _fused_loss(pred_mel, "speech", eos_weight, gold, lens)
 
     def head_of(pm, sp):
         if pm.stride(-1) == 1 and pm.stride(-2) == ldh and sp.data_ptr() == pm.data_ptr() + 4 * M and sp.stride(-1) == ldh \
@@ -279,21 +284,16 @@ def speech_loss(gold_mel, stop_label, pred_mel, post_pred_mel, mel_len, stop_pre
     def bwd(g, saved):
         head, post = saved
         if fused is not None:
-            known = _known_value(g)
-            if known is not None and abs(known - fused["gscale"]) <= 1e-12 * abs(known):
-                F.FUSED_STATS["speech_grad_direct"] += 1
+            if _fused_grad_applies(fused, g):
                 dh = fused["d_head"].view(B, T, ldh)
                 return dh[..., :M], fused["d_post"], dh[..., M]
-            F.FUSED_STATS["speech_grad_general"] += 1
             head = head_of(pred_mel.detach(), stop_pred.detach())
             post = post_pred_mel.detach().contiguous()
         dh = torch.empty(B, T, ldh, dtype=torch.float32, device=g.device)
         dp = torch.empty(B, T, M, dtype=torch.float32, device=g.device)
         ops.speech_loss_bwd(gold, head.view(B, T, ldh), post, lens, float(eos_weight), g, dh, dp)
         return dh[..., :M], dp, dh[..., M]
-    if fused is not None:
-        return _scalar_segment(fwd, bwd, pred_mel, post_pred_mel, stop_pred, loss_tensor=fused["loss"])
-    return _scalar_segment(fwd, bwd, pred_mel, post_pred_mel, stop_pred)
+    return _scalar_segment(fwd, bwd, pred_mel, post_pred_mel, stop_pred, loss_tensor=None if fused is None else fused["loss"])
 
 
 @on_stream("disc")

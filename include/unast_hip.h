@@ -272,6 +272,27 @@ int unast_lstm_bwd(const float* dy, const float* dhfinal, const float* whh, cons
 int unast_leaky_dropout(const float* x, const float* dy, float* out, int rows, int D, float slope, float drop_p, unsigned int seed,
                         unsigned int stream_id, hipStream_t stream);
 
+/* --- CBHG vocoder, eval forward (src/network.py:627-655 Vocoder, src/module.py:533-626 CBHG, 500-530 Highwaynet) --- */
+/* nn.Conv1d forward with 1..16 taps (stride 1, dilation 1) as an implicit GEMM on the MFMA pipe: the convolution bank and the two
+ * projections of CBHG (src/module.py:553-577, 605-607, 616-617).  X [B,T,Cin] (row stride ldx), Wp [Cout][taps][Cin] (tap-major),
+ * Y[b,t,o] = epi(sum_{j,c} X[b, t + j - pad_left, c] Wp[o][j][c]), zero outside [0, T) of each sequence -- with pad_left = taps / 2
+ * that is Conv1d(padding = taps // 2) followed by _conv_fit_dim (src/module.py:590-594).  Epilogue as unast_gemm: + bias[o] -> relu if
+ * act == 1 -> + R[(b,t), o] (R may be NULL).  Cin % 4 == 0; Y may be a column slice of a wider buffer (ldy).  With taps = 5 the launch is
+ * the one unast_gemm makes for its conv forward form (a_mode 1, b_mode 0). */
+int unast_conv_fwd(int nsplit, const float* X, int ldx, const float* Wp, float* Y, int ldy, int B, int T, int Cin, int Cout,
+                   int taps, int pad_left, const float* bias, int act, const float* R, int ldr, hipStream_t stream);
+/* nn.MaxPool1d(2, stride=1, padding=1)(x)[:, :, :-1] of CBHG (src/module.py:583, 613) on the token-major layout:
+ * out[b,t,:] = max(in[b,t-1,:], in[b,t,:]), out[b,0,:] = in[b,0,:].  C and the row strides are multiples of 4 floats. */
+int unast_maxpool_prev(const float* in, int ld_in, float* out, int ld_out, int B, int T, int C, hipStream_t stream);
+/* One Highwaynet layer behind its GEMM (src/module.py:524-528): ht [rows, 2C] = [linears.i(x) | gates.i(x)] (pre-activation),
+ * out = relu(h) * t + x * (1 - t) with t = sigmoid(.).  out may be x. */
+int unast_highway_combine(const float* ht, int ld_ht, const float* x, int ld_x, float* out, int ld_out, int rows, int C, hipStream_t stream);
+/* Recurrent part of CBHG's bidirectional nn.GRU (src/module.py:585-587, 623-624), hidden 128, gate order r,z,n, zero initial state,
+ * over ALL T positions of every row (no packing; the reverse direction starts at T-1), both directions in one launch.
+ * xproj [B,T,768] = per direction [xr | xz | xn] = X W_ih^T + b_ih, with b_hr and b_hz added as well; whh [2][384][128];
+ * b_hn [2][128]; y [B,T,256] = [forward | backward].  Nothing is saved for a backward. */
+int unast_gru_fwd(const float* xproj, const float* whh, const float* b_hn, float* y, int B, int T, int hidden, hipStream_t stream);
+
 /* Registers a 4-byte counter in device memory that every dropout / noise kernel adds to its stream id (NULL = none).  Launches
  * replayed from a captured HIP graph carry fixed (seed, stream_id) arguments; the generation loop of infer_sequence
  * (src/network.py:219-252, 455-481: fresh dropout masks at every decoded position when the model is in training mode)

@@ -632,15 +632,16 @@ static void launch_split(const GemmParams& p, int nsplit, int wn, int flags, dim
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-extern "C" int unast_gemm(int a_mode, int b_mode, int nsplit,
-                          const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                          int M, int N, int K, int kb_valid,
-                          int conv_T, int conv_ca, int conv_cb, int conv_shift,
-                          const float* bias, const float* R, int ldr, const float* G, int ldg, float gate_scale,
-                          float alpha, int beta, int act,
-                          float drop_p, unsigned int seed, unsigned int stream_id,
-                          int splitk, float* splitk_ws, int64_t splitk_ws_floats, float* rowsum_a, int tile_wn, int b_presplit,
-                          int out_split, double* colstats, hipStream_t stream) {
+// conv_ks: taps of the implicit-conv forms (unast_gemm: 5; unast_conv_fwd: 1..16).
+static int gemm_run(int a_mode, int b_mode, int nsplit,
+                    const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                    int M, int N, int K, int kb_valid,
+                    int conv_T, int conv_ca, int conv_cb, int conv_shift, int conv_ks,
+                    const float* bias, const float* R, int ldr, const float* G, int ldg, float gate_scale,
+                    float alpha, int beta, int act,
+                    float drop_p, unsigned int seed, unsigned int stream_id,
+                    int splitk, float* splitk_ws, int64_t splitk_ws_floats, float* rowsum_a, int tile_wn, int b_presplit,
+                    int out_split, double* colstats, hipStream_t stream) {
     UNAST_REQUIRE(A && B && C, "unast_gemm: null operand");
     UNAST_REQUIRE(!b_presplit || (a_mode == OP_KC || a_mode == OP_KC_CONV), "unast_gemm: a pre-split B is a weight (forward / dgrad forms only)");
     UNAST_REQUIRE(M > 0 && N > 0 && K > 0, "unast_gemm: bad dims M=%d N=%d K=%d", M, N, K);
@@ -659,7 +660,7 @@ extern "C" int unast_gemm(int a_mode, int b_mode, int nsplit,
     GemmParams p;
     p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.T = conv_T > 0 ? conv_T : 1; p.ca = conv_ca > 0 ? conv_ca : 1; p.cb = conv_cb > 0 ? conv_cb : 1;
-    p.shift = conv_shift; p.KS = 5;
+    p.shift = conv_shift; p.KS = conv_ks;
     p.bias = bias; p.R = R; p.ldr = ldr; p.G = G; p.ldg = ldg; p.gate_scale = gate_scale;
     p.alpha = alpha; p.beta = beta; p.act = act;
     p.drop_thresh = drop_threshold(drop_p); p.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
@@ -700,7 +701,7 @@ extern "C" int unast_gemm(int a_mode, int b_mode, int nsplit,
             p.atomic = 1;
         }
     }
-    if (a_mode == OP_KC_CONV) UNAST_REQUIRE((conv_ca & 3) == 0 && K == 5 * conv_ca && M % p.T == 0, "unast_gemm: bad conv A geometry");
+    if (a_mode == OP_KC_CONV) UNAST_REQUIRE((conv_ca & 3) == 0 && K == conv_ks * conv_ca && M % p.T == 0, "unast_gemm: bad conv A geometry");
     if (b_mode == OP_RC_CONV_DGRAD) UNAST_REQUIRE(K == 5 * conv_cb, "unast_gemm: bad conv dgrad geometry");
     if (b_mode == OP_RC_CONV_WGRAD) UNAST_REQUIRE((conv_cb & 3) == 0 && N == 5 * conv_cb && K % p.T == 0, "unast_gemm: bad conv wgrad geometry");
     p.nsplitk = splitk;
@@ -728,6 +729,33 @@ extern "C" int unast_gemm(int a_mode, int b_mode, int nsplit,
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p.slab, p.slab_stride, p.ld_slab, splitk, C, ldc, M, N, beta);
     }
     return unast_check_launch("unast_gemm");
+}
+
+extern "C" int unast_gemm(int a_mode, int b_mode, int nsplit,
+                          const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                          int M, int N, int K, int kb_valid,
+                          int conv_T, int conv_ca, int conv_cb, int conv_shift,
+                          const float* bias, const float* R, int ldr, const float* G, int ldg, float gate_scale,
+                          float alpha, int beta, int act,
+                          float drop_p, unsigned int seed, unsigned int stream_id,
+                          int splitk, float* splitk_ws, int64_t splitk_ws_floats, float* rowsum_a, int tile_wn, int b_presplit,
+                          int out_split, double* colstats, hipStream_t stream) {
+    return gemm_run(a_mode, b_mode, nsplit, A, lda, B, ldb, C, ldc, M, N, K, kb_valid, conv_T, conv_ca, conv_cb, conv_shift, 5,
+                    bias, R, ldr, G, ldg, gate_scale, alpha, beta, act, drop_p, seed, stream_id, splitk, splitk_ws, splitk_ws_floats,
+                    rowsum_a, tile_wn, b_presplit, out_split, colstats, stream);
+}
+
+// Forward conv1d with `taps` taps as the same implicit GEMM (the gather is generic in the tap index): Y[(b,t)][o] =
+// epi(sum_{j,c} X[b, t + j - pad_left, c] Wp[o][j][c]), zero outside [0, T) of each sequence.
+extern "C" int unast_conv_fwd(int nsplit, const float* X, int ldx, const float* Wp, float* Y, int ldy, int B, int T, int Cin, int Cout,
+                              int taps, int pad_left, const float* bias, int act, const float* R, int ldr, hipStream_t stream) {
+    UNAST_REQUIRE(taps >= 1 && taps <= 16, "unast_conv_fwd: 1..16 taps (got %d)", taps);
+    UNAST_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0 && (Cin & 3) == 0, "unast_conv_fwd: bad dims B=%d T=%d Cin=%d Cout=%d (Cin %% 4 == 0)", B, T, Cin, Cout);
+    UNAST_REQUIRE(pad_left >= 0 && pad_left < taps, "unast_conv_fwd: pad_left must be in [0, taps)");
+    UNAST_REQUIRE(ldx >= Cin && ldy >= Cout && (!R || ldr >= Cout), "unast_conv_fwd: row strides shorter than the rows");
+    UNAST_REQUIRE((long long)B * T <= 0x7FFFFFFF && (long long)taps * Cin <= 0x7FFFFFFF, "unast_conv_fwd: problem too large");
+    return gemm_run(OP_KC_CONV, OP_KC, nsplit, X, ldx, Wp, taps * Cin, Y, ldy, B * T, Cout, taps * Cin, 0, T, Cin, 0, pad_left, taps,
+                    bias, R, ldr, nullptr, 0, 1.f, 1.f, 0, act, 0.f, 0u, 0u, 1, nullptr, 0, nullptr, 0, 0, 0, nullptr, stream);
 }
 
 // Host side of the grouped weight-gradient launch.  items[i] = {A = dY_i [tokens][M_i] (row stride lda), B = X_i [tokens][N_i],

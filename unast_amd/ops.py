@@ -776,6 +776,59 @@ def leaky_dropout(x, dy, out, slope, drop_p=0.0, seed=0, stream_id=0):
           "unast_leaky_dropout")
 
 
+# ---- CBHG vocoder (eval forward) ---------------------------------------------------------------------------
+def conv_taps_fwd(x3d, Wp, bias, out, pad_left, act=0, R=None):
+    """x3d [B,T,Cin] (a column slice of a wider buffer is fine), Wp [Cout,taps,Cin] (tap-major, contiguous), out [B,T,Cout] (likewise a
+    slice): out[b,t] = epi(sum_j Wp[:,j,:] x[b, t + j - pad_left]), zero outside each sequence; epi = + bias -> relu if act -> + R."""
+    B, T, Cin = x3d.shape
+    Cout, taps, _ = Wp.shape
+    if not (Wp.is_contiguous() and Wp.shape[2] == Cin and x3d.stride(2) == 1 and out.stride(2) == 1 and x3d.stride(0) == T * x3d.stride(1)
+            and out.stride(0) == T * out.stride(1) and out.shape == (B, T, Cout)):
+        raise ValueError("conv_taps_fwd: tap-major contiguous weights and [B,T,C] operands with dense batch strides")
+    if (bias is not None and bias.numel() != Cout) or (R is not None and not (R.shape[-1] == Cout and R.numel() == B * T * Cout and R.stride(-1) == 1
+                                                                         and (R.dim() == 2 or R.stride(0) == T * R.stride(1)))):
+        raise ValueError("conv_taps_fwd: bias [Cout]; R [B*T, Cout] or [B,T,Cout] with dense batch strides")
+    if x3d.dtype is not _F32 or Wp.dtype is not _F32 or out.dtype is not _F32 or not out.is_cuda:
+        for t, n in ((x3d, "x"), (Wp, "W"), (out, "out"), (bias, "bias"), (R, "R")):
+            _f32(t, n)
+    check(lib().unast_conv_fwd(config.NSPLIT, _p(x3d), x3d.stride(1), _p(Wp), _p(out), out.stride(1), B, T, Cin, Cout, taps, pad_left,
+                               _p(bias), act, _p(R), R.stride(-2) if R is not None else 0, _stream()), "unast_conv_fwd")
+    return out
+
+
+def maxpool_prev(x3d, out3d):
+    """out[b,t] = max(x[b,t-1], x[b,t]) (out[b,0] = x[b,0])."""
+    B, T, C = x3d.shape
+    if not (out3d.shape == x3d.shape and x3d.stride(2) == 1 and out3d.stride(2) == 1 and x3d.stride(0) == T * x3d.stride(1)
+            and out3d.stride(0) == T * out3d.stride(1)):
+        raise ValueError("maxpool_prev: [B,T,C] operands of one shape with dense batch strides")
+    _f32(x3d, "x"), _f32(out3d, "out")
+    check(lib().unast_maxpool_prev(_p(x3d), x3d.stride(1), _p(out3d), out3d.stride(1), B, T, C, _stream()), "unast_maxpool_prev")
+    return out3d
+
+
+def highway_combine(ht, x, out):
+    """ht [rows, 2C] = [linear | gate] pre-activations, out = relu(h) * sigmoid(t) + x * (1 - sigmoid(t)); out may be x."""
+    rows, C = x.shape
+    if not (tuple(ht.shape) == (rows, 2 * C) and out.shape == x.shape and ht.stride(1) == 1 and x.stride(1) == 1 and out.stride(1) == 1):
+        raise ValueError("highway_combine: ht [rows, 2C], x and out [rows, C], unit column strides")
+    _f32(ht, "ht"), _f32(x, "x"), _f32(out, "out")
+    check(lib().unast_highway_combine(_p(ht), ht.stride(0), _p(x), x.stride(0), _p(out), out.stride(0), rows, C, _stream()), "unast_highway_combine")
+    return out
+
+
+def gru_fwd(xproj, whh, b_hn, y):
+    """xproj [B,T,768] (input projections of both directions, b_ih + [b_hr, b_hz, 0] added), whh [2,384,128], b_hn [2,128], y [B,T,256]."""
+    B, T = xproj.shape[0], xproj.shape[1]
+    if not (xproj.is_contiguous() and whh.is_contiguous() and b_hn.is_contiguous() and y.is_contiguous() and xproj.shape[2] == 768
+            and tuple(whh.shape) == (2, 384, 128) and tuple(y.shape) == (B, T, 256)):
+        raise ValueError("gru_fwd: contiguous xproj [B,T,768], whh [2,384,128], b_hn [2,128], y [B,T,256]")
+    for t, n in ((xproj, "xproj"), (whh, "whh"), (b_hn, "b_hn"), (y, "y")):
+        _f32(t, n)
+    check(lib().unast_gru_fwd(_p(xproj), _p(whh), _p(b_hn), _p(y), B, T, 128, _stream()), "unast_gru_fwd")
+    return y
+
+
 # ---- optimizer ---------------------------------------------------------------------------------------------
 _MSE_WS = {}
 

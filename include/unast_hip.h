@@ -261,8 +261,12 @@ int unast_randperm(int64_t* out, int n, unsigned int seed, unsigned int stream_i
 int unast_bce_logits(const float* logits, int ldx, const float* targets, int n, const float* gscale, float* loss, float* dlogits,
                      int ldd, hipStream_t stream);
 
-/* Recurrent part of nn.LSTM over packed sequences (src/module.py:306, 315-316), hidden 64, gate order i,f,g,o.
- * xproj [Bd,T,ndir*256] = X W_ih^T (no bias), y [Bd,T,ndir*64] and hprev pre-zeroed by the caller; gates/cs saved. */
+/* Recurrent part of nn.LSTM over packed sequences (src/module.py:306, 315-316), hidden H = 64 or 128, gate order i,f,g,o.
+ * One workgroup of 4 H threads per (sequence, direction): 256 threads at hidden 64, 512 at hidden 128; any other width is an error.
+ * xproj [Bd,T,ndir*4H] = X W_ih^T (no bias), y [Bd,T,ndir*H], gates [Bd,T,ndir,4H], cs / hprev [Bd,T,ndir,H] saved for the backward,
+ * hfinal [Bd,ndir*H], dgates [Bd,T,ndir,4H].  Steps t >= lens[b] are never computed; y, hprev and dgates of those steps are written
+ * as zeros by the kernels (the caller need not clear them), lens[b] = 0 gives hfinal = 0.  dy and dhfinal may each be NULL.
+ * (T + 9) * ndir * 16 H must fit 31 bits (a sequence's slab is addressed with 32-bit byte offsets, formed up to 9 steps past its end). */
 int unast_lstm_fwd(const float* xproj, const float* whh, const float* b_ih, const float* b_hh, const int* lens, float* y, float* gates,
                    float* cs, float* hprev, float* hfinal, int Bd, int T, int ndir, int hidden, int64_t whh_dir_stride,
                    int64_t bias_dir_stride, hipStream_t stream);

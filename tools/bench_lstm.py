@@ -1,9 +1,12 @@
-import os, sys, torch
+import argparse, os, sys, torch
 sys.path.insert(0, "/root/repo")
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "."))
 from unast_amd import ops
+ap = argparse.ArgumentParser()
+ap.add_argument("--hidden", type=int, choices=(64, 128), default=64, help="width of the recurrence (disc_hid); 128 runs the 512-thread kernels")
+a = ap.parse_args()
 D = torch.device("cuda:0")
-Bd, T, Hh = 64, 800, 64
+Bd, T, Hh = 64, 800, a.hidden
 g = torch.Generator().manual_seed(0)
 lens = torch.full((Bd,), T, dtype=torch.int32, device=D)
 whh = (torch.randn(2 * 4 * Hh, Hh, generator=g) * 0.1).to(D); bih = torch.zeros(2 * 4 * Hh, device=D); bhh = torch.zeros(2 * 4 * Hh, device=D)
@@ -20,4 +23,4 @@ def timeit(fn, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 f = timeit(lambda: ops.lstm_fwd(xproj, whh, bih, bhh, lens, y, gates, cs, hprev, hfin, 2, 4 * Hh * Hh, 4 * Hh))
 b = timeit(lambda: ops.lstm_bwd(dy, dhf, whh, gates, cs, lens, dg, 2, 4 * Hh * Hh))
-print("lstm fwd %.0f us (%.3f us/step)  bwd %.0f us (%.3f us/step)" % (f, f / T, b, b / T))
+print("lstm%s fwd %.0f us (%.3f us/step)  bwd %.0f us (%.3f us/step)" % ("" if Hh == 64 else " hidden=%d" % Hh, f, f / T, b, b / T))

@@ -9,7 +9,7 @@
 #include "common.h"
 #include "recur.h"
 
-#define LH 64             // hidden size
+#define LH 64             // hidden size (the kernels for hidden 128 follow these two)
 #define LG (4 * LH)       // gate rows
 
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
@@ -269,6 +269,231 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* __restrict__
     }
 }
 
+// ---- hidden 128 (disc_hid of the reference's transformer_d_test config) ----------------------------------------------------------------
+// The same two kernels at twice the width: 512 threads, WNW = 8 waves (two per SIMD, 256 registers per lane), wave w owns units
+// [16 w, 16 w + 16), lane 16 q + c is gate q of unit 16 w + c and holds its W_hh row (forward) or column (backward) as 128 floats in rotation
+// order -- the geometry of gru_fwd_kernel (vocoder.hip), with all four lane rows at work.  Per step: the wave's own 16 units from the register
+// in front of the barrier, the other seven waves' by one ds_read_b32 each behind it, ONE barrier.  Siblings, not a template over the
+// width: the H = 64 kernels above are the measured ones and stay as the compiler sees them today (generalising their source, with
+// identical arithmetic, already moves its register allocation and schedule); the knock-out switches stay with them too.  DESIGN 5f.
+#define WH 128            // hidden size
+#define WG (4 * WH)       // gate rows
+#define WNW (WH / 16)     // waves per workgroup
+#define WPS (WH / 64)     // waves that cover the WH units of one padded time step, 64 each
+// backward: timesteps of saved state per chunk (even: the LDS buffer's parity is i & 1).  Ten registers per step (six loaded values in
+// flight, four derived ones) share the lane's 256 with the 128 weights: 198 / 224 / 250 VGPRs at 4 / 6 / 8 steps, none with scratch, and
+// 692 / 701 / 705 us at 64 x 800 -- the shallowest chunk already hides the loads (a step is 0.87 us), and a deeper one only lengthens the prologue.
+#ifndef WBCH                 // (-DWBCH=6 / 8: the builds behind the other two figures)
+#define WBCH 4
+#endif
+
+__global__ __launch_bounds__(4 * WH) void lstm_fwd128_kernel(const float* __restrict__ xproj, const float* __restrict__ whh, const float* __restrict__ b_ih,
+                                                       const float* __restrict__ b_hh, const int* __restrict__ lens, float* __restrict__ y,
+                                                       float* __restrict__ gates, float* __restrict__ cs, float* __restrict__ hprev,
+                                                       float* __restrict__ hfinal, int T, int ndir, size_t whh_dir_stride, size_t bias_dir_stride) {
+    __shared__ __attribute__((aligned(16))) float h_lds[2][WH];
+    const int b = blockIdx.x, dir = blockIdx.y, j = threadIdx.x;
+    const int wave = j >> 6, lane = j & 63, q = lane >> 4, c16 = lane & 15;
+    const int u = 16 * wave + c16;                     // hidden unit of this lane
+    const int row = q * WH + u;                        // its gate row
+    const int len = lens[b];
+    // w[jw][n] = W_hh[row][16 ((wave + jw) % WNW) + src[n]]: the weights of source wave (wave + jw) % WNW in the order the rotations deliver h
+    float w[WNW][16];
+    int src[16];
+    RotSrc<0>::fill(c16, src);
+    const float* wr = whh + dir * whh_dir_stride + (size_t)row * WH;
+#pragma unroll
+    for (int jw = 0; jw < WNW; ++jw)
+#pragma unroll
+        for (int n = 0; n < 16; ++n) w[jw][n] = wr[16 * ((wave + jw) & (WNW - 1)) + src[n]];
+    const float bias = b_ih[dir * bias_dir_stride + row] + b_hh[dir * bias_dir_stride + row];
+    int hs[WNW];                                                      // (hs[0], this wave's own units, is unused: they are in a register)
+#pragma unroll
+    for (int jw = 1; jw < WNW; ++jw) hs[jw] = 16 * ((wave + jw) & (WNW - 1)) + c16;
+    if (j < WH) h_lds[0][j] = 0.f;
+    const int pu = 64 * (wave % WPS) + lane;                         // padded steps: WPS waves clear one, 64 units each (lane = unit here)
+    for (int t = max(len, 0) + wave / WPS; t < T; t += WNW / WPS) {
+        y[((size_t)b * T + t) * ((size_t)ndir * WH) + dir * WH + pu] = 0.f;
+        hprev[(((size_t)b * T + t) * ndir + dir) * WH + pu] = 0.f;
+    }
+    if (len <= 0) {                                                  // (uniform) empty sequence: final state = initial state
+        if (wave < WPS) hfinal[(size_t)b * (ndir * WH) + dir * WH + pu] = 0.f;
+        return;
+    }
+    __syncthreads();
+    float c = 0.f, h = 0.f;
+    const size_t xs = (size_t)ndir * WG;
+    const float* xp = xproj + (size_t)b * T * xs + (size_t)dir * WG + row;
+    const int tstep = dir ? -1 : 1;
+    const int t0 = dir ? len - 1 : 0;
+    // The activated gates leave through a buffer descriptor over this sequence's slab: the per-lane part of the address is fixed for the
+    // launch, the time step advances in a scalar register.
+    const bool writer = q == 0;                                      // one lane row per wave stores the unit's state
+    const __amdgpu_buffer_rsrc_t g_rs = __builtin_amdgcn_make_buffer_rsrc(gates + (size_t)b * T * ndir * WG, 0, (int)((size_t)T * ndir * WG * 4), 0x00020000);
+    const uint32_t g_vo = (uint32_t)(dir * WG + row) * 4u;
+    int g_so = t0 * ndir * WG * 4;                                   // scalar byte offset of the current time step
+    const int g_inc = tstep * ndir * WG * 4;
+    // sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 2 / (1 + 2^(-2 x log2 e)) - 1: one branch-free form with per-lane constants (lane row 2 = g)
+    const float act_m = (q == 2) ? -2.f * LOG2E : -LOG2E, act_s = (q == 2) ? 2.f : 1.f, act_o = (q == 2) ? -1.f : 0.f;
+    // The unit's state leaves in ONE store per step: lane row 0 writes c_t, row 1 y_t = h_t, row 2 hprev_t = h_{t-1} (every lane of the unit
+    // has all three), row 3 nothing -- three 16-lane stores cost three issue slots of the in-order wave.
+    const size_t st_row0 = ((size_t)b * T + t0) * ndir + dir;
+    float* st_p = q == 0 ? cs + st_row0 * WH + u : q == 1 ? y + ((size_t)b * T + t0) * ((size_t)ndir * WH) + dir * WH + u : hprev + st_row0 * WH + u;
+    const ptrdiff_t st_inc = (ptrdiff_t)tstep * ndir * WH;
+    float xc[FCH], xn[FCH];
+    auto load_chunk = [&](int s0, float (&x)[FCH]) {
+#pragma unroll
+        for (int i = 0; i < FCH; ++i) {
+            const int st = min(s0 + i, len - 1);                   // clamped: a fixed number of loads per chunk
+            x[i] = xp[(size_t)(t0 + st * tstep) * xs];
+        }
+    };
+    load_chunk(0, xn);
+    float accn[4] = {0.f, 0.f, 0.f, 0.f};                            // this wave's 16 units' share of the NEXT step's dot product (h = 0 before the first)
+    for (int s0 = 0; s0 < len; s0 += FCH) {
+#pragma unroll
+        for (int i = 0; i < FCH; ++i) xc[i] = xn[i] + bias;          // the only wait for global loads: once per chunk
+        if (s0 + FCH < len) load_chunk(s0 + FCH, xn);
+#pragma unroll
+        for (int i = 0; i < FCH; ++i) {
+            if (s0 + i < len) {                                      // (uniform; a guard, not a break, so that the chunk unrolls and xc[i] is a register)
+                const float* hl = h_lds[i & 1];                      // (FCH is even: the step's parity is i & 1)
+                float hv[WNW];                                        // the other waves' units, one value per lane; this wave's are in `h`
+#pragma unroll
+                for (int jw = 1; jw < WNW; ++jw) hv[jw] = hl[hs[jw]];
+                float acc[4] = {accn[0] + xc[i], accn[1], accn[2], accn[3]};
+#pragma unroll
+                for (int jw = 1; jw < WNW; ++jw) dot16<false, false>(w[jw], hv[jw], acc);
+                const float pre = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                const float act = __builtin_fmaf(__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(act_m * pre)), act_s, act_o);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(act), g_rs, g_vo, g_so, 0);
+                const float h_before = h;
+                float e16, o16, ig, gg, fg, og;
+                swap16(act, e16, o16);                               // rows (0, 1): (i, f); rows (2, 3): (g, o)
+                swap32(e16, ig, gg);
+                swap32(o16, fg, og);
+                c = fg * c + ig * gg;
+                h = og * __builtin_fmaf(__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f((-2.f * LOG2E) * c)), 2.f, -1.f);
+                if (q < 3) *st_p = q == 0 ? c : q == 1 ? h : h_before;
+                st_p += st_inc;
+                if (writer) h_lds[(i + 1) & 1][u] = h;
+                dot16<true, true>(w[0], h, accn);                                // the next step's share of this wave's own units: before the barrier
+                g_so += g_inc;
+                __syncthreads();
+            }
+        }
+    }
+    if (writer) hfinal[(size_t)b * (ndir * WH) + dir * WH + u] = h;
+}
+
+// Backward at hidden 128: lstm_bwd_kernel with 512 gate gradients in the LDS vector and column k of gate block q as 128 floats per lane.
+__global__ __launch_bounds__(4 * WH) void lstm_bwd128_kernel(const float* __restrict__ dy, const float* __restrict__ dhfinal, const float* __restrict__ whh,
+                                                       const float* __restrict__ gates, const float* __restrict__ cs, const int* __restrict__ lens,
+                                                       float* __restrict__ dgates, int T, int ndir, size_t whh_dir_stride) {
+    __shared__ __attribute__((aligned(16))) float dg_lds[2][WG];
+    const int b = blockIdx.x, dir = blockIdx.y, j = threadIdx.x;     // (blockDim.x == WG: thread j is also gate row j where rows are cleared)
+    const int len = lens[b];
+    const int wave = j >> 6, lane = j & 63, q = lane >> 4, c16 = lane & 15;
+    const int k = 16 * wave + c16;                  // this lane's hidden unit
+    // wt[jw][n] = W_hh[H q + 16 ((wave + jw) % WNW) + src[n]][k]: column k of gate block q, in the order the rotations deliver the gate gradients
+    float wt[WNW][16];
+    int src[16];
+    RotSrc<0>::fill(c16, src);
+    const float* wr = whh + dir * whh_dir_stride + (size_t)(q * WH) * WH + k;
+#pragma unroll
+    for (int jw = 0; jw < WNW; ++jw)
+#pragma unroll
+        for (int n = 0; n < 16; ++n) wt[jw][n] = wr[(size_t)(16 * ((wave + jw) & (WNW - 1)) + src[n]) * WH];
+    int ds[WNW];                                             // (ds[0], this wave's own gradients, is unused: they are in a register)
+#pragma unroll
+    for (int jw = 1; jw < WNW; ++jw) ds[jw] = q * WH + 16 * ((wave + jw) & (WNW - 1)) + c16;
+    float dh = 0.f, dc = 0.f;
+    if (dhfinal) dh = dhfinal[(size_t)b * (ndir * WH) + dir * WH + k];
+    const int tstep = dir ? 1 : -1;                         // reverse of the forward processing order
+    const int t0 = dir ? 0 : len - 1;
+    // r = 0..len-1 counts backward steps; forward step index = len-1-r; time t = t0 + r*tstep
+    // Saved state through buffer descriptors over this sequence's slabs: the per-lane part of every address is fixed for the launch, the
+    // time step is a scalar offset -- the 64-bit address arithmetic of 7 loads was a quarter of the step's vector instructions, and an
+    // in-order wave pays 4 cycles for each.  dy = NULL becomes a descriptor of zero records: its loads return 0.
+    const __amdgpu_buffer_rsrc_t gl_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gates) + (size_t)b * T * ndir * WG, 0, (int)((size_t)T * ndir * WG * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t cl_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cs) + (size_t)b * T * ndir * WH, 0, (int)((size_t)T * ndir * WH * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t yl_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy ? dy : cs) + (size_t)b * T * ndir * WH, 0, dy ? (int)((size_t)T * ndir * WH * 4) : 0, 0x00020000);
+    const int vo_g = (dir * WG + k) * 4, vo_c = (dir * WH + k) * 4;
+    auto ldf = [](const __amdgpu_buffer_rsrc_t& rs, int vo, int so) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, 0)); };
+    float vn[WBCH][6], cnext;                                // gates i f g o, c_t, dy_t of WBCH steps; c of the step after them
+    // The steps beyond the sequence are not clamped to its last one: their loads leave the slab at its end (the range check returns 0), stop
+    // at its first row, or read padded rows of it, and nothing computed from them is used.  Offsets advance by scalar adds.
+    const int g_incb = tstep * ndir * WG * 4, c_incb = tstep * ndir * WH * 4;
+    auto load_chunk = [&](int r0) {
+        int so_g = (t0 + r0 * tstep) * ndir * WG * 4, so_c = (t0 + r0 * tstep) * ndir * WH * 4;
+#pragma unroll
+        for (int i = 0; i < WBCH; ++i) {
+            const int sg = max(so_g, 0), sc = max(so_c, 0);        // (the forward direction walks down past t = 0: no negative offsets)
+            vn[i][0] = ldf(gl_rs, vo_g, sg); vn[i][1] = ldf(gl_rs, vo_g + WH * 4, sg); vn[i][2] = ldf(gl_rs, vo_g + 2 * WH * 4, sg); vn[i][3] = ldf(gl_rs, vo_g + 3 * WH * 4, sg);
+            vn[i][4] = ldf(cl_rs, vo_c, sc);
+            vn[i][5] = ldf(yl_rs, vo_c, sc);
+            so_g += g_incb; so_c += c_incb;
+        }
+        cnext = ldf(cl_rs, vo_c, max(so_c, 0));
+    };
+    for (int t = max(len, 0); t < T; ++t) dgates[(((size_t)b * T + t) * ndir + dir) * WG + j] = 0.f;       // padded steps: 16 H bytes per step
+    if (len <= 0) return;                                   // (uniform)
+    const __amdgpu_buffer_rsrc_t d_rs = __builtin_amdgcn_make_buffer_rsrc(dgates + (size_t)b * T * ndir * WG, 0, (int)((size_t)T * ndir * WG * 4), 0x00020000);
+    const uint32_t d_vo = (uint32_t)(dir * WG + q * WH + k) * 4u;
+    int d_so = t0 * ndir * WG * 4;                          // scalar byte offset of the current time step
+    const int d_inc = tstep * ndir * WG * 4;
+    const bool q0 = q == 0, q1 = q == 1, q2 = q == 2, is_o = q == 3;
+    load_chunk(0);
+    for (int r0 = 0; r0 < len; r0 += WBCH) {
+        // Per step, off the dependent chain: with dht = dh + dy and dct = dc + dht B, the gate gradient of this lane is X Y where
+        // X = dht (gate o) or dct (gates i, f, g) and Y = tc og (1 - og) (o), gg ig (1 - ig) (i), cprev fg (1 - fg) (f) or ig (1 - gg gg) (g):
+        // Y = m1 m2 (1 - m2), or m1 (1 - m2 m2) for g, with the operands picked per lane row; dc = dct fg.
+        float cy[WBCH], cB[WBCH], cf[WBCH], cd[WBCH];
+#pragma unroll
+        for (int i = 0; i < WBCH; ++i) {
+            const float ig = vn[i][0], fg = vn[i][1], gg = vn[i][2], og = vn[i][3];
+            const float cafter = i + 1 < WBCH ? vn[i + 1][4] : cnext;           // c of the previous FORWARD step = the next backward step's
+            const float cprev = (r0 + i >= len - 1) ? 0.f : cafter;           // (scalar condition; steps beyond the sequence are never used)
+            const float tc = tanhf_(vn[i][4]);
+            cB[i] = og * (1.f - tc * tc);
+            cf[i] = fg;
+            cd[i] = vn[i][5];
+            const float m1 = q0 ? gg : q1 ? cprev : q2 ? ig : tc;
+            const float m2 = q0 ? ig : q1 ? fg : q2 ? gg : og;
+            const float ya = m1 * m2, yb = 1.f - m2;                          // m1 m2 (1 - m2)
+            const float yc = 1.f - m2 * m2;                                   // m1 (1 - m2 m2)
+            cy[i] = q2 ? m1 * yc : ya * yb;
+        }
+        if (r0 + WBCH < len) load_chunk(r0 + WBCH);
+#pragma unroll
+        for (int i = 0; i < WBCH; ++i) {
+            const int r = r0 + i;
+            if (r < len) {                                  // (uniform; a guard, not a break, so that the chunk unrolls)
+            const float dht = dh + cd[i];
+            const float dct = __builtin_fmaf(dht, cB[i], dc);
+            dc = dct * cf[i];
+            const float mine = (is_o ? dht : dct) * cy[i];
+            float* dgw = dg_lds[i & 1];                     // (WBCH is even: the step's parity is i & 1)
+            dgw[q * WH + k] = mine;
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mine), d_rs, d_vo, d_so, 0);
+            d_so += d_inc;
+            float acc[4];
+            dot16<true, true>(wt[0], mine, acc);            // this wave's own 16 gradients: in front of the barrier, under the LDS write
+            __syncthreads();
+            float dv[WNW];                                   // gate type q of the other waves' units
+#pragma unroll
+            for (int jw = 1; jw < WNW; ++jw) dv[jw] = dgw[ds[jw]];
+#pragma unroll
+            for (int jw = 1; jw < WNW; ++jw) dot16<false, false>(wt[jw], dv[jw], acc);
+            float e16, o16, lo, up;
+            swap16((acc[0] + acc[1]) + (acc[2] + acc[3]), e16, o16);
+            swap32(e16 + o16, lo, up);
+            dh = lo + up;                                   // (i + f) + (g + o): the same sum in every lane of the unit
+            }
+        }
+    }
+}
+
 // y = dropout(leaky_relu(x, slope));  backward: dx = dy*mask/(1-p) * (x > 0 ? 1 : slope).  slope = 1 gives plain dropout.
 __global__ __launch_bounds__(256) void leaky_dropout_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, int rows, int D,
                                                             float slope, uint32_t drop_thresh, float drop_scale, uint32_t seed, uint32_t stream) {
@@ -286,20 +511,32 @@ extern "C" int unast_lstm_fwd(const float* xproj, const float* whh, const float*
                               float* cs, float* hprev, float* hfinal, int Bd, int T, int ndir, int hidden, int64_t whh_dir_stride,
                               int64_t bias_dir_stride, hipStream_t stream) {
     UNAST_REQUIRE(xproj && whh && b_ih && b_hh && lens && y && gates && cs && hprev && hfinal, "unast_lstm_fwd: null pointer");
-    UNAST_REQUIRE(hidden == LH, "unast_lstm_fwd: this build supports hidden=%d only (got %d)", LH, hidden);
+    UNAST_REQUIRE(hidden == LH || hidden == WH, "unast_lstm_fwd: this build supports hidden=%d and hidden=%d only (got %d)", LH, WH, hidden);
     UNAST_REQUIRE(Bd > 0 && T > 0 && (ndir == 1 || ndir == 2), "unast_lstm_fwd: bad dims");
     UNAST_REQUIRE((((uintptr_t)whh) & 15) == 0 && (whh_dir_stride & 3) == 0, "unast_lstm_fwd: W_hh must be 16-byte aligned");
-    hipLaunchKernelGGL(lstm_fwd_kernel, dim3(Bd, ndir), dim3(256), 0, stream, xproj, whh, b_ih, b_hh, lens, y, gates, cs, hprev, hfinal, T, ndir,
-                       (size_t)whh_dir_stride, (size_t)bias_dir_stride);
+    // (the kernels address a sequence's slabs through 32-bit byte offsets of T * ndir * 4 * hidden floats; + 9 steps: the backward forms the
+    // offsets of up to a chunk of 8 steps and one more beyond the sequence's end before it clamps them)
+    UNAST_REQUIRE((long long)(T + 9) * ndir * 16 * hidden <= 0x7FFFFFFFLL, "unast_lstm_fwd: T=%d is too long for 32-bit offsets into a sequence's slab", T);
+    if (hidden == LH)
+        hipLaunchKernelGGL(lstm_fwd_kernel, dim3(Bd, ndir), dim3(256), 0, stream, xproj, whh, b_ih, b_hh, lens, y, gates, cs, hprev, hfinal, T, ndir,
+                           (size_t)whh_dir_stride, (size_t)bias_dir_stride);
+    else
+        hipLaunchKernelGGL(lstm_fwd128_kernel, dim3(Bd, ndir), dim3(4 * WH), 0, stream, xproj, whh, b_ih, b_hh, lens, y, gates, cs, hprev, hfinal, T, ndir,
+                           (size_t)whh_dir_stride, (size_t)bias_dir_stride);
     return unast_check_launch("unast_lstm_fwd");
 }
 
 extern "C" int unast_lstm_bwd(const float* dy, const float* dhfinal, const float* whh, const float* gates, const float* cs, const int* lens,
                               float* dgates, int Bd, int T, int ndir, int hidden, int64_t whh_dir_stride, hipStream_t stream) {
     UNAST_REQUIRE(whh && gates && cs && lens && dgates, "unast_lstm_bwd: null pointer");
-    UNAST_REQUIRE(hidden == LH, "unast_lstm_bwd: this build supports hidden=%d only (got %d)", LH, hidden);
+    UNAST_REQUIRE(hidden == LH || hidden == WH, "unast_lstm_bwd: this build supports hidden=%d and hidden=%d only (got %d)", LH, WH, hidden);
     UNAST_REQUIRE(Bd > 0 && T > 0 && (ndir == 1 || ndir == 2), "unast_lstm_bwd: bad dims");
-    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(Bd, ndir), dim3(256), 0, stream, dy, dhfinal, whh, gates, cs, lens, dgates, T, ndir, (size_t)whh_dir_stride);
+    UNAST_REQUIRE((long long)(T + 9) * ndir * 16 * hidden <= 0x7FFFFFFFLL, "unast_lstm_bwd: T=%d is too long for 32-bit offsets into a sequence's slab", T);
+    if (hidden == LH)
+        hipLaunchKernelGGL(lstm_bwd_kernel, dim3(Bd, ndir), dim3(256), 0, stream, dy, dhfinal, whh, gates, cs, lens, dgates, T, ndir, (size_t)whh_dir_stride);
+    else
+        hipLaunchKernelGGL(lstm_bwd128_kernel, dim3(Bd, ndir), dim3(4 * WH), 0, stream, dy, dhfinal, whh, gates, cs, lens, dgates, T, ndir,
+                           (size_t)whh_dir_stride);
     return unast_check_launch("unast_lstm_bwd");
 }
 

@@ -474,8 +474,9 @@ class LSTMDiscriminator(_Side):
 
     def __init__(self, d_in, hidden, out=1, bidirectional=False, num_layers=1, dropout=.2, relu=.2):
         super().__init__()
-        if hidden != 64 or out != 1:
-            raise NotImplementedError("the persistent LSTM kernel is built for hidden=64, out=1 (disc_hid of every reference config)")
+        if hidden not in (64, 128) or out != 1:
+            raise NotImplementedError("the persistent LSTM kernels are built for hidden=64 and hidden=128 with out=1 (got hidden=%r, out=%r)"
+                                      % (hidden, out))
         self.num_dir = 2 if bidirectional else 1
         self.num_layers = num_layers
         self.hidden = hidden

@@ -757,15 +757,25 @@ def bce_logits(logits, ldx, targets, n, loss=None, gscale=None, dlogits=None, ld
 
 
 # ---- LSTM discriminator ------------------------------------------------------------------------------------
+def _lstm_hidden(whh, other, per_unit, name):
+    """The LSTM kernels' width: W_hh's row length, which the saved-state operand (4 H gate rows or H cell states per step) must share."""
+    H = whh.shape[-1]
+    if other.shape[-1] != per_unit * H:
+        raise ValueError("%s: W_hh has rows of %d but the state operand's last dimension is %d, not %d" % (name, H, other.shape[-1], per_unit * H))
+    return H
+
+
 def lstm_fwd(xproj, whh, b_ih, b_hh, lens_i32, y, gates, cs, hprev, hfinal, ndir, whh_dir_stride, bias_dir_stride):
     Bd, T = xproj.shape[0], xproj.shape[1]
+    H = _lstm_hidden(whh, cs, 1, "lstm_fwd")
     check(lib().unast_lstm_fwd(_p(xproj), _p(whh), _p(b_ih), _p(b_hh), _p(lens_i32), _p(y), _p(gates), _p(cs), _p(hprev), _p(hfinal), Bd, T,
-                               ndir, 64, whh_dir_stride, bias_dir_stride, _stream()), "unast_lstm_fwd")
+                               ndir, H, whh_dir_stride, bias_dir_stride, _stream()), "unast_lstm_fwd")
 
 
 def lstm_bwd(dy, dhfinal, whh, gates, cs, lens_i32, dgates, ndir, whh_dir_stride):
     Bd, T = gates.shape[0], gates.shape[1]
-    check(lib().unast_lstm_bwd(_p(dy), _p(dhfinal), _p(whh), _p(gates), _p(cs), _p(lens_i32), _p(dgates), Bd, T, ndir, 64, whh_dir_stride,
+    H = _lstm_hidden(whh, gates, 4, "lstm_bwd")
+    check(lib().unast_lstm_bwd(_p(dy), _p(dhfinal), _p(whh), _p(gates), _p(cs), _p(lens_i32), _p(dgates), Bd, T, ndir, H, whh_dir_stride,
                                _stream()), "unast_lstm_bwd")
 
 

@@ -1,6 +1,7 @@
 """CPU-side checks (no GPU): C-ABI library loads and exports every symbol of include/unast_hip.h, the host logic
 (state_dict contract, flat layout, schedules, RNG seeds, API errors) and the data-parallel gradient exchange (gloo, 2 ranks)."""
 import ctypes
+import json
 import os
 import subprocess
 import sys
@@ -237,6 +238,10 @@ def test_bucketed_gradient_exchange_two_ranks_gloo(tmp_path):
 
 def test_golden_fixtures_are_data_only(golden_dir):
     for f in os.listdir(golden_dir):
+        if f.endswith(".json"):             # a recorded call trace: JSON holds numbers, strings, lists and objects, nothing that runs
+            with open(os.path.join(golden_dir, f)) as fh:
+                json.load(fh)
+            continue
         assert f.endswith(".npz"), f
         z = np.load(os.path.join(golden_dir, f), allow_pickle=False)
         for k in z.files:

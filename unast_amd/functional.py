@@ -51,16 +51,6 @@ def _bias_grad(cx, dy2d, name_or_view):
 # Transformer sub-layers (torch.nn.TransformerEncoderLayer / DecoderLayer, post-LN, ReLU; src/module.py:273-274,
 # 286-287; exact math SURVEY.md Appendix A)
 # ---------------------------------------------------------------------------------------------------------------
-def _layernorm(cx, tape, z, pre, x_res_grad_sink):
-    """y = LN(z).  Backward returns (dz, dz_dropped) through `x_res_grad_sink(dz, dzd)`."""
-    rows, C = z.shape
-    y = _empty(rows, C, like=z)
-    mean = _empty(rows, like=z)
-    rstd = _empty(rows, like=z)
-    ops.layernorm_fwd(z, cx.P[pre + "weight"], cx.P[pre + "bias"], y, mean, rstd, LN_EPS)
-    return y, mean, rstd
-
-
 def _ln_backward(cx, out, z, mean, rstd, pre_norm, p, seed, stream_id):
     """(dz, dz_dropped-or-dz) of the LayerNorm that produced `out`: already there when the consuming sub-layer's last GEMM ran it in its
     epilogue (out.pre, _input_grad below), otherwise the stand-alone kernel on out.g."""
@@ -95,106 +85,86 @@ def _input_grad(cx, x, dy2d, W, dz_res):
     acc(x, dx)
 
 
-def attn_sublayer(cx, tape, x, mem, lens_k, causal, pre_attn, pre_norm, B, Tq, Tk, H, drop, pad_free_grads=False):
-    """y = LN(x + dropout(MHA(x, mem or x)))  with attention-probability dropout `drop` as well.
-    x: Var [B*Tq, E]; mem: Var [B*Tk, E] or None for self-attention."""
+def attn_sublayer(cx, tape, x, lens, causal, pre_attn, pre_norm, B, T, H, drop, pad_free_grads=False):
+    """y = LN(x + dropout(MHA(x, x)))  with attention-probability dropout `drop` as well (self-attention; cross_attn_sublayer is the
+    decoder's other one).  x: Var [B*T, E]."""
     E = x.v.shape[1]
-    Nq, Nk = B * Tq, B * Tk
+    N = B * T
     W, bias = cx.P[pre_attn + "in_proj_weight"], cx.P[pre_attn + "in_proj_bias"]
     Wo, bo = cx.P[pre_attn + "out_proj.weight"], cx.P[pre_attn + "out_proj.bias"]
     p = cx.p(drop)
     s_attn, s_out = cx.stream(), cx.stream()
     # Q / K / V (and dO below) are read by the attention kernels only: the projections store them pre-split (hi/lo bf16 chunks), so
     # the K/V tiles every query block stages -- and Q / dO in the backward -- need no fp32 -> hi/lo conversion there
-    if mem is None:
-        qkv = _empty(Nq, 3 * E, like=x.v)
-        ops.linear_fwd(x.v, W, bias, qkv, out_split=True)
-        Q, K, V = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
-    else:
-        q = _empty(Nq, E, like=x.v)
-        kv = _empty(Nk, 2 * E, like=x.v)
-        ops.linear_fwd(x.v, W[:E], bias[:E], q, out_split=True)
-        ops.linear_fwd(mem.v, W[E:], bias[E:], kv, out_split=True)
-        Q, K, V = q, kv[:, :E], kv[:, E:]
-    O = _empty(Nq, E, like=x.v)
-    LSE = _empty(B, H, Tq, like=x.v)
-    ops.attn_fwd(Q, K, V, O, LSE, lens_k, B, H, Tq, Tk, causal, drop_p=p, seed=cx.seed, stream_id=s_attn, qkv_split=True)
-    z = _empty(Nq, E, like=x.v)
-    y, mean, rstd = _empty(Nq, E, like=x.v), _empty(Nq, like=x.v), _empty(Nq, like=x.v)
+    qkv = _empty(N, 3 * E, like=x.v)
+    ops.linear_fwd(x.v, W, bias, qkv, out_split=True)
+    Q, K, V = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+    O = _empty(N, E, like=x.v)
+    LSE = _empty(B, H, T, like=x.v)
+    ops.attn_fwd(Q, K, V, O, LSE, lens, B, H, T, T, causal, drop_p=p, seed=cx.seed, stream_id=s_attn, qkv_split=True)
+    z = _empty(N, E, like=x.v)
+    y, mean, rstd = _empty(N, E, like=x.v), _empty(N, like=x.v), _empty(N, like=x.v)
     # z = x + drop(O Wo^T + bo), y = LayerNorm(z): one launch where the row-panel GEMM serves the shape, GEMM + LayerNorm otherwise
     ops.linear_fwd(O, Wo, bo, z, drop_p=p, seed=cx.seed, stream_id=s_out, R=x.v, ln=(cx.P[pre_norm + "weight"], cx.P[pre_norm + "bias"], y, mean, rstd, LN_EPS))
     out = Var(y)
     if tape is not None:
         seed = cx.seed
 
-        out.ln = (z, mean, rstd, pre_norm, p, seed, s_out)      # (used only if a stack loop declares the next sub-layer the sole consumer: _sole)
+        out.ln = (z, mean, rstd, pre_norm, p, seed, s_out)      # (used only while the next sub-layer is its sole consumer: the stack loops clear it on their output)
 
         def bwd():
             if out.g is None and out.pre is None:
                 return
             with ops.wgrad_batch():            # out-proj + in-proj weight gradients: one grouped launch at the end
-                bwd_body()
-
-        def bwd_body():
-            st = cx.st
-            dz, da = _ln_backward(cx, out, z, mean, rstd, pre_norm, p, seed, s_out)
-            gWo = st.g(pre_attn + "out_proj.weight")
-            if gWo is not None:
-                ops.linear_wgrad(da, O, gWo, db=st.g(pre_attn + "out_proj.bias"))
-            dO = _empty(Nq, E, like=z)
-            ops.linear_dgrad(da, Wo, dO, out_split=True)
-            delta = _empty(B, H, Tq, like=z)
-            gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
-            if mem is None:
-                dqkv = _empty(Nq, 3 * E, like=z)
-                ops.attn_bwd(Q, K, V, O, dO, LSE, delta, dqkv[:, :E], dqkv[:, E:2 * E], dqkv[:, 2 * E:], lens_k, B, H, Tq, Tk, causal,
-                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=True, lens_q=lens_k if (pad_free_grads and config.ENC_SKIP_PAD_GRADS) else None)
+                st = cx.st
+                dz, da = _ln_backward(cx, out, z, mean, rstd, pre_norm, p, seed, s_out)
+                gWo = st.g(pre_attn + "out_proj.weight")
+                if gWo is not None:
+                    ops.linear_wgrad(da, O, gWo, db=st.g(pre_attn + "out_proj.bias"))
+                dO = _empty(N, E, like=z)
+                ops.linear_dgrad(da, Wo, dO, out_split=True)
+                delta = _empty(B, H, T, like=z)
+                gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
+                dqkv = _empty(N, 3 * E, like=z)
+                ops.attn_bwd(Q, K, V, O, dO, LSE, delta, dqkv[:, :E], dqkv[:, E:2 * E], dqkv[:, 2 * E:], lens, B, H, T, T, causal,
+                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=True, lens_q=lens if (pad_free_grads and config.ENC_SKIP_PAD_GRADS) else None)
                 if gW is not None:
                     ops.linear_wgrad(dqkv, x.v, gW, db=gb)
                 _input_grad(cx, x, dqkv, W, dz)
-            else:
-                dq = _empty(Nq, E, like=z)
-                dkv = _empty(Nk, 2 * E, like=z)
-                ops.attn_bwd(Q, K, V, O, dO, LSE, delta, dq, dkv[:, :E], dkv[:, E:], lens_k, B, H, Tq, Tk, causal,
-                             drop_p=p, seed=seed, stream_id=s_attn, qkv_split=True)
-                if gW is not None:
-                    ops.linear_wgrad(dq, x.v, gW[:E], db=gb[:E])
-                    ops.linear_wgrad(dkv, mem.v, gW[E:], db=gb[E:])
-                _input_grad(cx, x, dq, W[:E], dz)           # (contraction over 256: the K-streamed kernel does not serve it; plain path)
-                dmem = _empty(Nk, E, like=z)
-                ops.linear_dgrad(dkv, W[E:], dmem)
-                acc(mem, dmem)
         tape.record(bwd)
     return out
 
 
-def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_norm, B, Tq, H, drop):
-    """The cross-attention sub-layer of TWO decoder calls of one query shape and the same weights (the auto-encoder and the supervised
-    sub-step's decoder, /root/reference/src/train.py:609-628): y = LN(x + dropout(MHA(x, mem_h))) for the two row blocks of x2 [2 B Tq, E]
-    with their own memories mems[h] (Var [B Tk_h, E]).  Everything that does not see the memory runs once over both blocks -- the query
-    projection, the out-projection + LayerNorm, their backward GEMMs and weight gradients; the K/V projections and the attention core
-    run per block."""
-    E = x2.v.shape[1]
+def cross_attn_sublayer(cx, tape, x, mems, lens_ks, Tks, pre_attn, pre_norm, B, Tq, H, drop):
+    """The cross-attention sub-layer of n decoder calls of one query shape and the same weights (one call, or the auto-encoder's and the
+    supervised sub-step's decoder of one generator phase, /root/reference/src/train.py:609-628): y = LN(x + dropout(MHA(x, mem_h))) for
+    the n row blocks of x [n B Tq, E] with their own memories mems[h] (Var [B Tk_h, E]).  Everything that does not see the memory runs
+    once over all blocks -- the query projection, the out-projection + LayerNorm, their backward GEMMs and weight gradients; the K/V
+    projections and the attention core run per block."""
+    n = len(mems)
+    E = x.v.shape[1]
     N = B * Tq
+    blk = lambda t, h: t[h * N:(h + 1) * N]
     W, bias = cx.P[pre_attn + "in_proj_weight"], cx.P[pre_attn + "in_proj_bias"]
     Wo, bo = cx.P[pre_attn + "out_proj.weight"], cx.P[pre_attn + "out_proj.bias"]
     p = cx.p(drop)
-    s_attn, s_out = (cx.stream(), cx.stream()), cx.stream()
-    q2 = _empty(2 * N, E, like=x2.v)
-    ops.linear_fwd(x2.v, W[:E], bias[:E], q2, out_split=True)
+    s_attn, s_out = [cx.stream() for _ in range(n)], cx.stream()
+    # Q / K / V (and dO below) pre-split for the attention kernels, as in attn_sublayer
+    q = _empty(n * N, E, like=x.v)
+    ops.linear_fwd(x.v, W[:E], bias[:E], q, out_split=True)
     kvs = []
-    for h in range(2):
-        kv = _empty(B * Tks[h], 2 * E, like=x2.v)
+    for h in range(n):
+        kv = _empty(B * Tks[h], 2 * E, like=x.v)
         ops.linear_fwd(mems[h].v, W[E:], bias[E:], kv, out_split=True)
         kvs.append(kv)
-    O2 = _empty(2 * N, E, like=x2.v)
-    LSE2 = _empty(2, B, H, Tq, like=x2.v)
-    for h in range(2):
-        ops.attn_fwd(q2[h * N:(h + 1) * N], kvs[h][:, :E], kvs[h][:, E:], O2[h * N:(h + 1) * N], LSE2[h], lens_ks[h], B, H, Tq, Tks[h], False,
+    O = _empty(n * N, E, like=x.v)
+    LSE = _empty(n, B, H, Tq, like=x.v)
+    for h in range(n):
+        ops.attn_fwd(blk(q, h), kvs[h][:, :E], kvs[h][:, E:], blk(O, h), LSE[h], lens_ks[h], B, H, Tq, Tks[h], False,
                      drop_p=p, seed=cx.seed, stream_id=s_attn[h], qkv_split=True)
-    z = _empty(2 * N, E, like=x2.v)
-    y, mean, rstd = _empty(2 * N, E, like=x2.v), _empty(2 * N, like=x2.v), _empty(2 * N, like=x2.v)
-    ops.linear_fwd(O2, Wo, bo, z, drop_p=p, seed=cx.seed, stream_id=s_out, R=x2.v, ln=(cx.P[pre_norm + "weight"], cx.P[pre_norm + "bias"], y, mean, rstd, LN_EPS))
+    z = _empty(n * N, E, like=x.v)
+    y, mean, rstd = _empty(n * N, E, like=x.v), _empty(n * N, like=x.v), _empty(n * N, like=x.v)
+    ops.linear_fwd(O, Wo, bo, z, drop_p=p, seed=cx.seed, stream_id=s_out, R=x.v, ln=(cx.P[pre_norm + "weight"], cx.P[pre_norm + "bias"], y, mean, rstd, LN_EPS))
     out = Var(y)
     if tape is not None:
         seed = cx.seed
@@ -204,22 +174,22 @@ def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_nor
         def bwd():
             if out.g is None and out.pre is None:
                 return
+            st = cx.st
+            gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
+            dkvs = []
             with ops.wgrad_batch():
-                st = cx.st
                 dz, da = _ln_backward(cx, out, z, mean, rstd, pre_norm, p, seed, s_out)
                 gWo = st.g(pre_attn + "out_proj.weight")
                 if gWo is not None:
-                    ops.linear_wgrad(da, O2, gWo, db=st.g(pre_attn + "out_proj.bias"))
-                dO = _empty(2 * N, E, like=z)
+                    ops.linear_wgrad(da, O, gWo, db=st.g(pre_attn + "out_proj.bias"))
+                dO = _empty(n * N, E, like=z)
                 ops.linear_dgrad(da, Wo, dO, out_split=True)
-                gW, gb = st.g(pre_attn + "in_proj_weight"), st.g(pre_attn + "in_proj_bias")
-                dq2 = _empty(2 * N, E, like=z)
-                dkvs = []
-                for h in range(2):
+                dq = _empty(n * N, E, like=z)
+                for h in range(n):
                     delta = _empty(B, H, Tq, like=z)
                     dkv = _empty(B * Tks[h], 2 * E, like=z)
-                    ops.attn_bwd(q2[h * N:(h + 1) * N], kvs[h][:, :E], kvs[h][:, E:], O2[h * N:(h + 1) * N], dO[h * N:(h + 1) * N], LSE2[h], delta,
-                                 dq2[h * N:(h + 1) * N], dkv[:, :E], dkv[:, E:], lens_ks[h], B, H, Tq, Tks[h], False,
+                    ops.attn_bwd(blk(q, h), kvs[h][:, :E], kvs[h][:, E:], blk(O, h), blk(dO, h), LSE[h], delta,
+                                 blk(dq, h), dkv[:, :E], dkv[:, E:], lens_ks[h], B, H, Tq, Tks[h], False,
                                  drop_p=p, seed=seed, stream_id=s_attn[h], qkv_split=True)
                     dkvs.append(dkv)
                     dmem = _empty(B * Tks[h], E, like=z)
@@ -227,63 +197,15 @@ def cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, pre_attn, pre_nor
                     acc(mems[h], dmem)
                 if gW is not None:
                     ops.linear_wgrad(dkvs[0], mems[0].v, gW[E:], db=gb[E:])
-                    ops.linear_wgrad(dq2, x2.v, gW[:E], db=gb[:E])
-                _input_grad(cx, x2, dq2, W[:E], dz)          # (contraction over 256: plain path)
-            # the second memory's K/V weight gradient accumulates into the SAME rows of in_proj_weight as the first's: the problems of a
-            # grouped launch run side by side, so it goes out on its own, behind the group (same stream: ops keeps a gradient buffer's stream)
-            gW = cx.st.g(pre_attn + "in_proj_weight")
+                    ops.linear_wgrad(dq, x.v, gW[:E], db=gb[:E])
+                _input_grad(cx, x, dq, W[:E], dz)           # (contraction over 256: the K-streamed kernel does not serve it; plain path)
+            # the later memories' K/V weight gradients accumulate into the SAME rows of in_proj_weight as the first's: the problems of a
+            # grouped launch run side by side, so they go out on their own, behind the group (same stream: ops keeps a gradient buffer's stream)
             if gW is not None:
-                ops.linear_wgrad(dkvs[1], mems[1].v, gW[E:], db=cx.st.g(pre_attn + "in_proj_bias")[E:])
+                for h in range(1, n):
+                    ops.linear_wgrad(dkvs[h], mems[h].v, gW[E:], db=gb[E:])
         tape.record(bwd)
     return out
-
-
-def decoder_stack_pair(cx, tape, x2, lens_q2, mems, lens_ks, Tks, pre, L, B, Tq, H, drop):
-    """decoder_stack over two calls of one query shape at once: causal self-attention and the feed-forward block over 2B sequences, the
-    cross-attention per call on its own memory (cross_attn_sublayer_pair)."""
-    for i in range(L):
-        lp = "%s%d." % (pre, i)
-        x2 = attn_sublayer(cx, tape, x2, None, lens_q2, True, lp + "self_attn.", lp + "norm1.", 2 * B, Tq, Tq, H, drop)
-        x2 = cross_attn_sublayer_pair(cx, tape, x2, mems, lens_ks, Tks, lp + "multihead_attn.", lp + "norm2.", B, Tq, H, drop)
-        x2 = ffn_sublayer(cx, tape, x2, lp, lp + "norm3.", drop)
-    x2.ln = None                # the stack's output has consumers outside it: its LayerNorm backward stays a launch of its own
-    return x2
-
-
-def speech_decode_pair(cx, tape, m, mels, lens_q2, mems, lens_ks, Tks, loss_hints):
-    """SpeechTransformer.decode_sequence of TWO calls of one target shape (the auto-encoder's and the TTS decoder of one generator phase):
-    front ends per call into one buffer, the decoder stack once over both (decoder_stack_pair), heads + post-net + loss terms per call
-    (the post-net's BatchNorm statistics stay per call, first a, then b).  Returns [(head Var, post Var)] per call."""
-    B, T, M = mels[0].shape
-    a = m.args
-    N = B * T
-    E = cx.P["speech_m.prenet.layer.fc2.linear_layer.weight"].shape[0]
-    buf = _empty(2 * N, E, like=mels[0])
-    halves = [speech_decode_front(cx, tape, m, mels[h], True, out=buf[h * N:(h + 1) * N]) for h in range(2)]
-    x2 = _stack_rows(cx, tape, halves, buf)
-    y2 = decoder_stack_pair(cx, tape, x2, lens_q2, mems, lens_ks, Tks, "speech_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, a.nhead, a.d_drop)
-    # the two tails read row blocks of y2 and put their d(loss)/dx straight into row blocks of ONE gradient buffer
-    gbuf = {}
-    xs = [Var(y2.v[h * N:(h + 1) * N]) for h in range(2)]
-    if tape is not None:
-        def join():                                   # recorded before the tails => runs after them: hand the buffer to the stack
-            if "g" in gbuf:
-                for h in range(2):
-                    if xs[h].g is None:
-                        gbuf["g"][h * N:(h + 1) * N].zero_()
-                    elif xs[h].g.data_ptr() != gbuf["g"][h * N:(h + 1) * N].data_ptr():
-                        ops.sum2(gbuf["g"][h * N:(h + 1) * N], xs[h].g.contiguous())
-                acc(y2, gbuf["g"])
-        tape.record(join)
-
-    def dx_block(h):
-        def get():
-            if "g" not in gbuf:
-                gbuf["g"] = _empty(2 * N, E, like=y2.v)
-            return gbuf["g"][h * N:(h + 1) * N]
-        return get
-    outs = [speech_decode_tail(cx, tape, m, xs[h], mels[h], postnet=True, loss_hint=loss_hints[h], dx_out=dx_block(h)) for h in range(2)]
-    return outs
 
 
 def ffn_sublayer(cx, tape, x, pre, pre_norm, drop):
@@ -338,28 +260,58 @@ def encoder_stack(cx, tape, x, lens, pre, L, B, T, H, drop):
     """src/module.py:270-280 (TransformerEncoder): all-False attn mask + key padding mask."""
     for i in range(L):
         lp = "%s%d." % (pre, i)
-        x = attn_sublayer(cx, tape, x, None, lens, False, lp + "self_attn.", lp + "norm1.", B, T, T, H, drop, pad_free_grads=True)
+        x = attn_sublayer(cx, tape, x, lens, False, lp + "self_attn.", lp + "norm1.", B, T, H, drop, pad_free_grads=True)
         x = ffn_sublayer(cx, tape, x, lp, lp + "norm2.", drop)
     x.ln = None                 # the stack's output has consumers outside it (decoder memory, discriminator): plain LayerNorm backward
     return x
 
 
-def decoder_stack(cx, tape, x, lens_q, mem, lens_k, pre, L, B, Tq, Tk, H, drop):
-    """src/module.py:283-293 (TransformerDecoder): causal + tgt padding self-attention, memory-padding cross-attention."""
+def decoder_stack(cx, tape, x, lens_q, mems, lens_ks, Tks, pre, L, B, Tq, H, drop):
+    """src/module.py:283-293 (TransformerDecoder) over the n = len(mems) calls of one query shape whose rows x holds [n B Tq, E]: causal +
+    tgt padding self-attention and the feed-forward block over n B sequences, memory-padding cross-attention per call on its own memory."""
+    n = len(mems)
     for i in range(L):
         lp = "%s%d." % (pre, i)
-        x = attn_sublayer(cx, tape, x, None, lens_q, True, lp + "self_attn.", lp + "norm1.", B, Tq, Tq, H, drop)
-        x = attn_sublayer(cx, tape, x, mem, lens_k, False, lp + "multihead_attn.", lp + "norm2.", B, Tq, Tk, H, drop)
+        x = attn_sublayer(cx, tape, x, lens_q, True, lp + "self_attn.", lp + "norm1.", n * B, Tq, H, drop)
+        x = cross_attn_sublayer(cx, tape, x, mems, lens_ks, Tks, lp + "multihead_attn.", lp + "norm2.", B, Tq, H, drop)
         x = ffn_sublayer(cx, tape, x, lp, lp + "norm3.", drop)
-    x.ln = None
+    x.ln = None                 # the stack's output has consumers outside it: its LayerNorm backward stays a launch of its own
     return x
+
+
+def _row_block_tails(tape, y, n, tail):
+    """[tail(h, x_h, dx_out_h)] for the n row blocks x_h of a decoder stack's output y (Var [n N, E]).  The tails write their input gradient
+    into row blocks of ONE buffer (dx_out_h() hands out block h), which goes to the stack as it is: with one block the tail's gradient is
+    the buffer, and nothing is launched here."""
+    N, E = y.v.shape[0] // n, y.v.shape[1]
+    gbuf = {}
+    xs = [Var(y.v[h * N:(h + 1) * N]) for h in range(n)]
+    if tape is not None:
+        def join():                                   # recorded before the tails => runs after them: hand the buffer to the stack
+            if "g" in gbuf:
+                for h in range(n):
+                    blk = gbuf["g"][h * N:(h + 1) * N]
+                    if xs[h].g is None:
+                        blk.zero_()
+                    elif xs[h].g.data_ptr() != blk.data_ptr():
+                        ops.sum2(blk, xs[h].g.contiguous())
+                acc(y, gbuf["g"])
+        tape.record(join)
+
+    def dx_block(h):
+        def get():
+            if "g" not in gbuf:
+                gbuf["g"] = _empty(n * N, E, like=y.v)
+            return gbuf["g"][h * N:(h + 1) * N]
+        return get
+    return [tail(h, xs[h], dx_block(h)) for h in range(n)]
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # Positional encoding (src/module.py:249-267; dropout fixed at 0.1)
 # ---------------------------------------------------------------------------------------------------------------
 def posenc(cx, tape, x, pe, T, gate=None, out=None):
-    """out: an [N, Dm] row block of a larger buffer that receives the result (the two halves of a paired encoder call)."""
+    """out: an [N, Dm] row block of a larger buffer that receives the result (the blocks of an n-ary encoder / decoder call)."""
     N, Dm = x.v.shape
     p = cx.p(0.1)
     s = cx.stream()
@@ -399,7 +351,7 @@ class ZeroPool:
         return w
 
 
-def conv_bn_act(cx, tape, x, B, T, conv_pre, bn_pre, pad_left, act, drop, bn_buffers, residual=None, x_ld_view=None, pool=None):
+def conv_bn_act(cx, tape, x, B, T, conv_pre, bn_pre, pad_left, act, drop, bn_buffers, pool=None):
     """dropout(act(BN_train(conv1d_k5(x)))) — one stage of TextPrenet.forward_fcn / SpeechPostnet.forward
     (src/module.py:162-165, 223-230).  x: Var [B*T, Cin]."""
     Wp, b = cx.P[conv_pre + "conv.weight"], cx.P[conv_pre + "conv.bias"]
@@ -481,43 +433,35 @@ def text_frontend(cx, tape, m, ids, noise, out=None):
     return posenc(cx, tape, x, m.pe, T, out=out)
 
 
-def text_encode(cx, tape, m, ids, lens, noise):
-    """TextTransformer.encode (src/network.py:427-444)."""
-    B, T = ids.shape
-    a = m.args
-    x = text_frontend(cx, tape, m, ids, noise)
-    return encoder_stack(cx, tape, x, lens, "text_m.encoder.transformer_encoder.layers.", a.num_layers, B, T, a.nhead, a.e_drop)
-
-
-def _stack_rows(cx, tape, halves, buf):
-    """Var over `buf` [2N, E], whose two row blocks the front ends of a paired encoder call have just written (posenc out=): the
-    gradient that comes back for the whole buffer is handed to the halves as row-block views (no copy either way)."""
-    x2 = Var(buf)
+def _stack_rows(cx, tape, blocks, buf):
+    """Var over `buf` [n N, E], whose n row blocks the front ends of an n-ary encoder / decoder call have just written (posenc out=): the
+    gradient that comes back for the whole buffer is handed to the blocks as row-block views (no copy either way)."""
+    x = Var(buf)
     if tape is not None:
-        N = halves[0].v.shape[0]
+        N = blocks[0].v.shape[0]
 
         def bwd():
-            if x2.g is None:
+            if x.g is None:
                 return
-            for i, h in enumerate(halves):
-                acc(h, x2.g[i * N:(i + 1) * N])
-        tape.record(bwd)                                # recorded after the halves' own closures => runs before them
-    return x2
+            for i, h in enumerate(blocks):
+                acc(h, x.g[i * N:(i + 1) * N])
+        tape.record(bwd)                                # recorded after the blocks' own closures => runs before them
+    return x
 
 
-def text_encode_pair(cx, tape, m, ids_a, noise_a, ids_b, noise_b, lens2):
-    """TextTransformer.encode of TWO batches of one shape (the auto-encoder and the supervised sub-step of one generator phase, same
-    weights: /root/reference/src/train.py:609-628) with the encoder stack run ONCE over 2B sequences.  What the reference keeps per call
-    stays per half: the conv front end with its BatchNorm batch statistics and running-stat updates (first a, then b), the dropout /
-    noise streams.  Returns the stack's output Var [2 B T, E] (rows of a, then rows of b)."""
-    B, T = ids_a.shape
+def text_encode(cx, tape, m, ids, noises, lens):
+    """TextTransformer.encode (src/network.py:427-444) of the n batches `ids` of one shape (one call; or the auto-encoder's and the
+    supervised sub-step's of one generator phase, same weights: /root/reference/src/train.py:609-628) with the encoder stack run ONCE over
+    n B sequences (`lens`: their n B lengths).  What the reference keeps per call stays per block: the conv front end with its BatchNorm
+    batch statistics and running-stat updates (in call order), the dropout / noise streams.  Returns the stack's output Var [n B T, E]."""
+    n = len(ids)
+    B, T = ids[0].shape
     a = m.args
     E = cx.P["text_m.prenet.embed.weight"].shape[1]
-    buf = _empty(2 * B * T, E, device=ids_a.device)
-    xa = text_frontend(cx, tape, m, ids_a, noise_a, out=buf[:B * T])
-    xb = text_frontend(cx, tape, m, ids_b, noise_b, out=buf[B * T:])
-    x2 = _stack_rows(cx, tape, (xa, xb), buf)
-    return encoder_stack(cx, tape, x2, lens2, "text_m.encoder.transformer_encoder.layers.", a.num_layers, 2 * B, T, a.nhead, a.e_drop)
+    buf = _empty(n * B * T, E, device=ids[0].device)
+    blocks = [text_frontend(cx, tape, m, ids[h], noises[h], out=buf[h * B * T:(h + 1) * B * T]) for h in range(n)]
+    x = _stack_rows(cx, tape, blocks, buf)
+    return encoder_stack(cx, tape, x, lens, "text_m.encoder.transformer_encoder.layers.", a.num_layers, n * B, T, a.nhead, a.e_drop)
 
 
 FUSED_STATS = {"text_head": 0, "text_grad_direct": 0, "text_grad_general": 0, "speech_head": 0, "speech_grad_direct": 0, "speech_grad_general": 0}      # launches so far (tests)
@@ -530,56 +474,29 @@ def _hint_conforms(dev, eos_w, gscale, *tensors):
         torch.is_tensor(t) and t.dtype == dt and t.device == dev and t.numel() == n and t.is_contiguous() for t, dt, n in tensors)
 
 
-def text_decode(cx, tape, m, ids, lens_q, mem, lens_k, Tk, shift=True, loss_hint=None):
-    """TextTransformer.decode_sequence (src/network.py:483-493) incl. TextPostnet (src/module.py:233-246).
-    Returns Var logits buffer [B*T, 48] (46 valid columns).  shift=False: `ids` are the decoder inputs as they are
+def text_decode(cx, tape, m, ids, lens_q, mems, lens_ks, Tks, shift=True, loss_hints=None):
+    """TextTransformer.decode_sequence (src/network.py:483-493) incl. TextPostnet (src/module.py:233-246) of the n calls `ids` of one
+    target shape (one call; or the auto-encoder's text decoder and the ASR decoder of one generator phase): embeddings + positional
+    encoding per call into one buffer, the decoder stack once over all, TextPostnet head + loss per call.
+    Returns the n Var logits buffers [B*T, 48] (46 valid columns).  shift=False: `ids` are the decoder inputs as they are
     (TextTransformer.decode, src/network.py:446-450)."""
-    B, T = ids.shape
-    a = m.args
-    x = text_embed(cx, tape, ids, T, a.t_pre_drop, False, 1 if shift else -1)          # SOS_IDX = 1
-    x = posenc(cx, tape, x, m.pe, T)
-    x = decoder_stack(cx, tape, x, lens_q, mem, lens_k, "text_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, Tk, a.nhead, a.d_drop)
-    return text_decode_tail(cx, tape, m, x, loss_hint=loss_hint)
-
-
-def text_decode_pair(cx, tape, m, ids2, lens_q2, mems, lens_ks, Tks, loss_hints):
-    """TextTransformer.decode_sequence of TWO calls of one target shape (the auto-encoder's text decoder and the ASR decoder of one generator
-    phase): embeddings + positional encoding per call into one buffer, the decoder stack once over both (decoder_stack_pair), TextPostnet
-    head + loss per call.  Returns the two logits Vars."""
-    B, T = ids2[0].shape
+    n = len(ids)
+    B, T = ids[0].shape
     a = m.args
     N = B * T
     E = cx.P["text_m.prenet.embed.weight"].shape[1]
-    buf = _empty(2 * N, E, device=ids2[0].device)
-    halves = [posenc(cx, tape, text_embed(cx, tape, ids2[h], T, a.t_pre_drop, False, 1), m.pe, T, out=buf[h * N:(h + 1) * N]) for h in range(2)]
-    x2 = _stack_rows(cx, tape, halves, buf)
-    y2 = decoder_stack_pair(cx, tape, x2, lens_q2, mems, lens_ks, Tks, "text_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, a.nhead, a.d_drop)
-    gbuf = {}
-    xs = [Var(y2.v[h * N:(h + 1) * N]) for h in range(2)]
-    if tape is not None:
-        def join():                                   # recorded before the tails => runs after them
-            if "g" in gbuf:
-                for h in range(2):
-                    blk = gbuf["g"][h * N:(h + 1) * N]
-                    if xs[h].g is None:
-                        blk.zero_()
-                    elif xs[h].g.data_ptr() != blk.data_ptr():
-                        ops.sum2(blk, xs[h].g.contiguous())
-                acc(y2, gbuf["g"])
-        tape.record(join)
-
-    def dx_block(h):
-        def get():
-            if "g" not in gbuf:
-                gbuf["g"] = _empty(2 * N, E, like=y2.v)
-            return gbuf["g"][h * N:(h + 1) * N]
-        return get
-    return [text_decode_tail(cx, tape, m, xs[h], loss_hint=loss_hints[h], dx_out=dx_block(h)) for h in range(2)]
+    buf = _empty(n * N, E, device=ids[0].device)
+    blocks = [posenc(cx, tape, text_embed(cx, tape, ids[h], T, a.t_pre_drop, False, 1 if shift else -1), m.pe, T, out=buf[h * N:(h + 1) * N])
+              for h in range(n)]                                                        # SOS_IDX = 1
+    x = _stack_rows(cx, tape, blocks, buf)
+    y = decoder_stack(cx, tape, x, lens_q, mems, lens_ks, Tks, "text_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, a.nhead, a.d_drop)
+    hints = loss_hints or [None] * n
+    return _row_block_tails(tape, y, n, lambda h, xh, dx_out: text_decode_tail(cx, tape, m, xh, loss_hint=hints[h], dx_out=dx_out))
 
 
 def text_decode_tail(cx, tape, m, x, loss_hint=None, dx_out=None):
     """TextPostnet (dropout + fc1, src/module.py:233-246) on decoder states x (Var [B*T, E]), with the loss in the head's launch when the
-    step announced it.  dx_out: where the backward puts d(loss)/dx (a row block of a paired call's gradient buffer)."""
+    step announced it.  dx_out: where the backward puts d(loss)/dx (_row_block_tails)."""
     a = m.args
     N, E = x.v.shape
     p = cx.p(a.t_post_drop)
@@ -677,25 +594,17 @@ def speech_frontend(cx, tape, m, mel, noise, out=None):
     return speech_prenet(cx, tape, m, mel2d, T, out=out)
 
 
-def speech_encode(cx, tape, m, mel, lens, noise):
-    """SpeechTransformer.encode (src/network.py:203-208)."""
-    B, T, M = mel.shape
-    a = m.args
-    x = speech_frontend(cx, tape, m, mel, noise)
-    return encoder_stack(cx, tape, x, lens, "speech_m.encoder.transformer_encoder.layers.", a.num_layers, B, T, a.nhead, a.e_drop)
-
-
-def speech_encode_pair(cx, tape, m, mel_a, noise_a, mel_b, noise_b, lens2):
-    """SpeechTransformer.encode of two batches of one shape with the encoder stack run once over 2B sequences (see text_encode_pair; the
-    speech front end has no batch statistics, its dropout / noise streams stay per half)."""
-    B, T, M = mel_a.shape
+def speech_encode(cx, tape, m, mels, noises, lens):
+    """SpeechTransformer.encode (src/network.py:203-208) of the n batches `mels` of one shape with the encoder stack run once over n B
+    sequences (see text_encode; the speech front end has no batch statistics, its dropout / noise streams stay per call)."""
+    n = len(mels)
+    B, T, M = mels[0].shape
     a = m.args
     E = cx.P["speech_m.prenet.layer.fc2.linear_layer.weight"].shape[0]
-    buf = _empty(2 * B * T, E, like=mel_a)
-    xa = speech_frontend(cx, tape, m, mel_a, noise_a, out=buf[:B * T])
-    xb = speech_frontend(cx, tape, m, mel_b, noise_b, out=buf[B * T:])
-    x2 = _stack_rows(cx, tape, (xa, xb), buf)
-    return encoder_stack(cx, tape, x2, lens2, "speech_m.encoder.transformer_encoder.layers.", a.num_layers, 2 * B, T, a.nhead, a.e_drop)
+    buf = _empty(n * B * T, E, like=mels[0])
+    blocks = [speech_frontend(cx, tape, m, mels[h], noises[h], out=buf[h * B * T:(h + 1) * B * T]) for h in range(n)]
+    x = _stack_rows(cx, tape, blocks, buf)
+    return encoder_stack(cx, tape, x, lens, "speech_m.encoder.transformer_encoder.layers.", a.num_layers, n * B, T, a.nhead, a.e_drop)
 
 
 def speech_decode_front(cx, tape, m, mel, shift=True, out=None):
@@ -713,23 +622,40 @@ def speech_decode_front(cx, tape, m, mel, shift=True, out=None):
     return speech_prenet(cx, tape, m, tgt.view(N, M), T, out=out)
 
 
-def speech_decode(cx, tape, m, mel, lens_q, mem, lens_k, Tk, shift=True, postnet=True, loss_hint=None):
-    """SpeechTransformer.decode_sequence (src/network.py:254-269) + SpeechPostnet (src/module.py:155-171).
-    Returns (head Var [B*T, 84]: cols 0..79 pre-net mel, col 80 stop logit; post Var [B*T, 80]).
-    shift=False feeds `mel` as the decoder input as it is, postnet=False stops at the heads (SpeechTransformer.decode,
+def speech_decode(cx, tape, m, mels, lens_q, mems, lens_ks, Tks, shift=True, postnet=True, loss_hints=None):
+    """SpeechTransformer.decode_sequence (src/network.py:254-269) + SpeechPostnet (src/module.py:155-171) of the n calls `mels` of one
+    target shape (one call; or the auto-encoder's and the TTS decoder of one generator phase): front ends per call into one buffer, the
+    decoder stack once over all, heads + post-net + loss terms per call (the post-net's BatchNorm statistics stay per call, in call order).
+    Returns per call (head Var [B*T, 84]: cols 0..79 pre-net mel, col 80 stop logit; post Var [B*T, 80]).
+    shift=False feeds `mels` as the decoder input as they are, postnet=False stops at the heads (SpeechTransformer.decode,
     src/network.py:210-214; no tape)."""
-    B, T, M = mel.shape
+    n = len(mels)
+    B, T, M = mels[0].shape
     a = m.args
-    x = speech_decode_front(cx, tape, m, mel, shift)
-    x = decoder_stack(cx, tape, x, lens_q, mem, lens_k, "speech_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, Tk, a.nhead, a.d_drop)
-    return speech_decode_tail(cx, tape, m, x, mel, postnet=postnet, loss_hint=loss_hint)
+    N = B * T
+    E = cx.P["speech_m.prenet.layer.fc2.linear_layer.weight"].shape[0]
+    buf = _empty(n * N, E, like=mels[0])
+    blocks = [speech_decode_front(cx, tape, m, mels[h], shift, out=buf[h * N:(h + 1) * N]) for h in range(n)]
+    x = _stack_rows(cx, tape, blocks, buf)
+    y = decoder_stack(cx, tape, x, lens_q, mems, lens_ks, Tks, "speech_m.decoder.transformer_decoder.layers.", a.num_layers, B, T, a.nhead, a.d_drop)
+    hints = loss_hints or [None] * n
+    return _row_block_tails(tape, y, n, lambda h, xh, dx_out: speech_decode_tail(cx, tape, m, xh, mels[h], postnet=postnet, loss_hint=hints[h], dx_out=dx_out))
+
+
+def _postnet_convs(cx, tape, m, x, B, T, pool=None):
+    """The four conv + BatchNorm + tanh stages of SpeechPostnet (src/module.py:155-171) on x (Var [B*T, >= num_mels]); `pool`: their fp64
+    scratch where the caller keeps one (ZeroPool)."""
+    y = conv_bn_act(cx, tape, x, B, T, "speech_m.postnet.conv1.", "speech_m.postnet.pre_batchnorm.", 4, 2, m.args.s_post_drop, m.buffers_dict, pool=pool)
+    for i in range(3):
+        y = conv_bn_act(cx, tape, y, B, T, "speech_m.postnet.conv_list.%d." % i, "speech_m.postnet.batch_norm_list.%d." % i, 4, 2,
+                        m.args.s_post_drop, m.buffers_dict, pool=pool)
+    return y
 
 
 def speech_decode_tail(cx, tape, m, x, mel, postnet=True, loss_hint=None, dx_out=None):
     """The heads ([linear_project | stop_linear]) and the SpeechPostnet on decoder states x (Var [B*T, E]); mel only gives shapes / device.
-    dx_out: where the backward puts d(loss)/dx (a row block of a paired call's gradient buffer) instead of a buffer of its own."""
+    dx_out: where the backward puts d(loss)/dx (_row_block_tails) instead of a buffer of its own."""
     B, T, M = mel.shape
-    a = m.args
     N = B * T
     E = x.v.shape[1]
     st = cx.st
@@ -776,10 +702,7 @@ def speech_decode_tail(cx, tape, m, x, mel, postnet=True, loss_hint=None, dx_out
     if not postnet:
         return headv, None
     pool = ZeroPool(4, cx.P["speech_m.postnet.conv1.conv.weight"].shape[0], mel.device) if cx.training else None
-    y = conv_bn_act(cx, tape, pre, B, T, "speech_m.postnet.conv1.", "speech_m.postnet.pre_batchnorm.", 4, 2, a.s_post_drop, m.buffers_dict, pool=pool)
-    for i in range(3):
-        y = conv_bn_act(cx, tape, y, B, T, "speech_m.postnet.conv_list.%d." % i, "speech_m.postnet.batch_norm_list.%d." % i, 4, 2,
-                        a.s_post_drop, m.buffers_dict, pool=pool)
+    y = _postnet_convs(cx, tape, m, pre, B, T, pool=pool)
     Wp2, b2 = cx.P["speech_m.postnet.conv2.conv.weight"], cx.P["speech_m.postnet.conv2.conv.bias"]
     post = _empty(B, T, M, like=mel)
     C = y.v.shape[1]
@@ -963,13 +886,9 @@ def speech_postnet_residual(cx, m, mel3d, residual=True):
     """mel + SpeechPostnet(mel) for a [B,T,M] tensor (src/network.py:246; BN in the model's current mode); residual=False:
     SpeechPostnet(mel) alone (SpeechTransformer.postprocess, src/network.py:216-217).  No tape."""
     B, T, M = mel3d.shape
-    a = m.args
     N = B * T
     x = Var(mel3d.reshape(N, M))
-    y = conv_bn_act(cx, None, x, B, T, "speech_m.postnet.conv1.", "speech_m.postnet.pre_batchnorm.", 4, 2, a.s_post_drop, m.buffers_dict)
-    for i in range(3):
-        y = conv_bn_act(cx, None, y, B, T, "speech_m.postnet.conv_list.%d." % i, "speech_m.postnet.batch_norm_list.%d." % i, 4, 2,
-                        a.s_post_drop, m.buffers_dict)
+    y = _postnet_convs(cx, None, m, x, B, T)
     Wp2, b2 = cx.P["speech_m.postnet.conv2.conv.weight"], cx.P["speech_m.postnet.conv2.conv.bias"]
     post = _empty(B, T, M, like=mel3d)
     C = y.v.shape[1]

@@ -85,10 +85,58 @@ class _Side(nn.Module):
 
 
 class AutoEncoderNet(_Side):
-    """src/network.py:12-86 (abstract interface)."""
+    """src/network.py:12-86 (abstract interface), and what the text and the speech transformer share here: one n-ary code path for their
+    encoder and decoder calls (n = 1: encode / decode_sequence; n = 2: encode_pair / decode_pair).  Subclasses name their side (`_side`),
+    their functional.*_encode / *_decode (`_f_encode`, `_f_decode`) and turn a decoder call's result into output Vars (`_dec_outputs`)."""
 
     def preprocess(self, input_, input_lens):
         raise Exception("Please use a subclass for text or speech")
+
+    def _encode_n(self, calls):
+        """calls: [(input_, input_lens, noise_in)] of ONE shape: the front ends per call (BatchNorm statistics and running-stat updates in
+        call order, as separate calls would make them), the encoder stack once over all.  Returns [(enc_outputs, masks)] per call."""
+        n = len(calls)
+        if any(c[0].shape != calls[0][0].shape for c in calls):
+            raise ValueError("encode_pair: the two batches must have one shape")
+        B, T = calls[0][0].shape[:2]
+        lens = [lens_i32(c[1], c[0].device) for c in calls]
+        lens_all = lens[0] if n == 1 else torch.cat(lens)       # (one call: its length vector as it is, no copy launch)
+        cx = self._ctx()
+        ins = [c[0].detach().contiguous() for c in calls]
+        noises = [c[2] for c in calls]
+
+        def run(tape, dummy):
+            y = self._f_encode(cx, tape, self, ins, noises, lens_all)
+            if n == 2:
+                return _pair_outputs(tape, y, B, T)
+            o = _out3d(tape, y, B, T)
+            return [o, _alias(tape, o)]
+        outs = run_segment(run, ddp_hook(self._side + "_enc", cx.st), cx.st.dummy)
+        return [(outs[2 * i], (None, lens[i], outs[2 * i + 1])) for i in range(n)]
+
+    def _decode_n(self, calls):
+        """calls: [(tgt, tgt_lens, enc_outputs, masks, loss_hint)] with the targets in ONE shape: the decoder stack once over all
+        (self-attention and feed-forward over n B sequences, cross-attention per call on its own memory), front ends, heads and loss terms per
+        call.  Returns the calls' output tensors in call order, as run_segment gives them."""
+        n = len(calls)
+        if any(c[0].shape != calls[0][0].shape for c in calls):
+            raise ValueError("decode_pair: the two targets must have one shape")
+        B, T = calls[0][0].shape[:2]
+        Tks = [c[2].shape[1] for c in calls]
+        lq = [lens_i32(c[1], c[0].device) for c in calls]
+        lens_q = lq[0] if n == 1 else torch.cat(lq)
+        lens_ks = [c[3][1] for c in calls]
+        cx = self._ctx()
+        tgts = [c[0].detach().contiguous() for c in calls]
+        hints = [c[4] for c in calls]
+
+        def run(tape, dummy, *mem_in):
+            mems = [_mem_in(tape, mem, B, Tk) for mem, Tk in zip(mem_in, Tks)]
+            res = []
+            for out in self._f_decode(cx, tape, self, tgts, lens_q, mems, lens_ks, Tks, loss_hints=hints):
+                res += self._dec_outputs(tape, out, B, T)
+            return res
+        return run_segment(run, ddp_hook(self._side + "_dec", cx.st), cx.st.dummy, *[c[2] for c in calls])
 
 
 def _lens_of_pad_mask(mask, T, device):
@@ -212,90 +260,40 @@ class TextTransformer(AutoEncoderNet):
     def pe(self):
         return self.pos_emb.pe[0]
 
+    _side, _f_encode, _f_decode = "text", staticmethod(F.text_encode), staticmethod(F.text_decode)
+
     @on_stream("text")
     def encode(self, input_, input_lens, noise_in=False):
-        B, T = input_.shape
-        lens = lens_i32(input_lens, input_.device)
-        cx = self._ctx()
-        ids = input_.contiguous()
-
-        def run(tape, dummy):
-            o = _out3d(tape, F.text_encode(cx, tape, self, ids, lens, noise_in), B, T)
-            return [o, _alias(tape, o)]
-        enc, enc_hid = run_segment(run, ddp_hook("text_enc", cx.st), cx.st.dummy)
-        return enc, (None, lens, enc_hid)
+        return self._encode_n([(input_, input_lens, noise_in)])[0]
 
     @on_stream("text")
     def encode_pair(self, in_a, lens_a, noise_a, in_b, lens_b, noise_b):
-        """encode(in_a, lens_a, noise_a) and encode(in_b, lens_b, noise_b) of two batches of ONE shape as a single call: the front ends
-        per batch (BatchNorm statistics and running-stat updates in the order a, b, as two calls would make them), the encoder stack once
-        over both (unast_amd.functional.text_encode_pair).  Returns the two (enc_outputs, masks) pairs of the separate calls."""
-        if in_a.shape != in_b.shape:
-            raise ValueError("encode_pair: the two batches must have one shape")
-        B, T = in_a.shape
-        la, lb = lens_i32(lens_a, in_a.device), lens_i32(lens_b, in_b.device)
-        lens2 = torch.cat([la, lb])
-        cx = self._ctx()
-        ids_a, ids_b = in_a.contiguous(), in_b.contiguous()
+        """encode(in_a, lens_a, noise_a) and encode(in_b, lens_b, noise_b) of two batches of ONE shape as a single call (_encode_n).
+        Returns the two (enc_outputs, masks) pairs of the separate calls."""
+        return tuple(self._encode_n([(in_a, lens_a, noise_a), (in_b, lens_b, noise_b)]))
 
-        def run(tape, dummy):
-            return _pair_outputs(tape, F.text_encode_pair(cx, tape, self, ids_a, noise_a, ids_b, noise_b, lens2), B, T)
-        ea, ha, eb, hb = run_segment(run, ddp_hook("text_enc", cx.st), cx.st.dummy)
-        return (ea, (None, la, ha)), (eb, (None, lb, hb))
+    def _dec_outputs(self, tape, out, B, T):
+        """The logits output Var [B, T, V] over a call's padded logits buffer."""
+        V = self.postnet.fc1.weight.shape[0]
+        ldl = out.v.shape[1]
+        o = Var(out.v.view(B, T, ldl)[..., :V])
+        if tape is not None:
+            def bwd():
+                if o.g is not None:
+                    out.g = _as_padded(o.g, B * T, ldl, V)
+            tape.record(bwd)                                                    # recorded last => runs first
+        return [o]
 
     @on_stream("text")
     def decode_sequence(self, tgt, tgt_lens, enc_outputs, masks, teacher_ratio=1, loss_hint=None):
         """loss_hint (not in the reference's signature; unast_amd.train passes it): (gold, eos_weight, gscale, workspace) of the text_loss call
         that will follow on this call's logits -- the head GEMM then computes that loss and its gradient in the same launch."""
-        B, T = tgt.shape
-        Tk = enc_outputs.shape[1]
-        lens_q = lens_i32(tgt_lens, tgt.device)
-        lens_k = masks[1]
-        cx = self._ctx()
-        ids = tgt.contiguous()
-        V = self.postnet.fc1.weight.shape[0]
-
-        def run(tape, dummy, mem):
-            memv = _mem_in(tape, mem, B, Tk)
-            out = F.text_decode(cx, tape, self, ids, lens_q, memv, lens_k, Tk, loss_hint=loss_hint)
-            ldl = out.v.shape[1]
-            o = Var(out.v.view(B, T, ldl)[..., :V])
-            if tape is not None:
-                def bwd():
-                    if o.g is not None:
-                        out.g = _as_padded(o.g, B * T, ldl, V)
-                tape.record(bwd)                                                    # recorded last => runs first
-            return [o]
-        return run_segment(run, ddp_hook("text_dec", cx.st), cx.st.dummy, enc_outputs)
+        return self._decode_n([(tgt, tgt_lens, enc_outputs, masks, loss_hint)])
 
     @on_stream("text")
     def decode_pair(self, tgt_a, lens_a, enc_a, masks_a, hint_a, tgt_b, lens_b, enc_b, masks_b, hint_b):
-        """Two decode_sequence calls of one target shape as a single call (see SpeechTransformer.decode_pair): the decoder stack once over
-        both, cross-attention per call on its own memory, head + loss per call.  Returns the two logits tensors."""
-        if tgt_a.shape != tgt_b.shape:
-            raise ValueError("decode_pair: the two targets must have one shape")
-        B, T = tgt_a.shape
-        Tks = (enc_a.shape[1], enc_b.shape[1])
-        lq = torch.cat([lens_i32(lens_a, tgt_a.device), lens_i32(lens_b, tgt_b.device)])
-        lens_ks = (masks_a[1], masks_b[1])
-        cx = self._ctx()
-        ids2 = (tgt_a.contiguous(), tgt_b.contiguous())
-        V = self.postnet.fc1.weight.shape[0]
-
-        def run(tape, dummy, mem_a, mem_b):
-            mems = (_mem_in(tape, mem_a, B, Tks[0]), _mem_in(tape, mem_b, B, Tks[1]))
-            res = []
-            for out in F.text_decode_pair(cx, tape, self, ids2, lq, mems, lens_ks, Tks, (hint_a, hint_b)):
-                ldl = out.v.shape[1]
-                o = Var(out.v.view(B, T, ldl)[..., :V])
-                if tape is not None:
-                    def bwd(o=o, out=out, ldl=ldl):
-                        if o.g is not None:
-                            out.g = _as_padded(o.g, B * T, ldl, V)
-                    tape.record(bwd)
-                res.append(o)
-            return res
-        return run_segment(run, ddp_hook("text_dec", cx.st), cx.st.dummy, enc_a, enc_b)
+        """Two decode_sequence calls of one target shape as a single call (_decode_n).  Returns the two logits tensors."""
+        return self._decode_n([(tgt_a, lens_a, enc_a, masks_a, hint_a), (tgt_b, lens_b, enc_b, masks_b, hint_b)])
 
     @on_stream("text")
     def decode(self, tgt, tgt_lens, tgt_pad_mask, enc_outputs, enc_mask):
@@ -307,7 +305,7 @@ class TextTransformer(AutoEncoderNet):
         lens_k = _lens_of_pad_mask(enc_mask, Tk, tgt.device)
         cx = self._ctx()
         with torch.no_grad():
-            out = F.text_decode(cx, None, self, tgt.contiguous(), lens_q, Var(enc_outputs.detach().contiguous().view(B * Tk, -1)), lens_k, Tk, shift=False)
+            out, = F.text_decode(cx, None, self, [tgt.contiguous()], lens_q, [Var(enc_outputs.detach().contiguous().view(B * Tk, -1))], [lens_k], [Tk], shift=False)
         V = self.postnet.fc1.weight.shape[0]
         return out.v.view(B, T, -1)[:, -1:, :V]
 
@@ -355,76 +353,34 @@ class SpeechTransformer(AutoEncoderNet):
     def pe(self):
         return self.pos_emb.pe[0]
 
+    _side, _f_encode, _f_decode = "speech", staticmethod(F.speech_encode), staticmethod(F.speech_decode)
+
     @on_stream("speech")
     def encode(self, input_, input_lens, noise_in=False):
-        B, T, M = input_.shape
-        lens = lens_i32(input_lens, input_.device)
-        cx = self._ctx()
-        mel = input_.detach().contiguous()
-
-        def run(tape, dummy):
-            o = _out3d(tape, F.speech_encode(cx, tape, self, mel, lens, noise_in), B, T)
-            return [o, _alias(tape, o)]
-        enc, enc_hid = run_segment(run, ddp_hook("speech_enc", cx.st), cx.st.dummy)
-        return enc, (None, lens, enc_hid)
+        return self._encode_n([(input_, input_lens, noise_in)])[0]
 
     @on_stream("speech")
     def encode_pair(self, in_a, lens_a, noise_a, in_b, lens_b, noise_b):
-        """Two encode calls of one shape as one (see TextTransformer.encode_pair): front ends per batch, the encoder stack once over both."""
-        if in_a.shape != in_b.shape:
-            raise ValueError("encode_pair: the two batches must have one shape")
-        B, T, M = in_a.shape
-        la, lb = lens_i32(lens_a, in_a.device), lens_i32(lens_b, in_b.device)
-        lens2 = torch.cat([la, lb])
-        cx = self._ctx()
-        mel_a, mel_b = in_a.detach().contiguous(), in_b.detach().contiguous()
+        """Two encode calls of one shape as one (see TextTransformer.encode_pair)."""
+        return tuple(self._encode_n([(in_a, lens_a, noise_a), (in_b, lens_b, noise_b)]))
 
-        def run(tape, dummy):
-            return _pair_outputs(tape, F.speech_encode_pair(cx, tape, self, mel_a, noise_a, mel_b, noise_b, lens2), B, T)
-        ea, ha, eb, hb = run_segment(run, ddp_hook("speech_enc", cx.st), cx.st.dummy)
-        return (ea, (None, la, ha)), (eb, (None, lb, hb))
+    def _dec_outputs(self, tape, out, B, T):
+        head, post = out
+        return _speech_outputs(tape, head, post, B, T, post.v.shape[1], head.v.device)
 
     @on_stream("speech")
     def decode_sequence(self, tgt, tgt_lens, enc_outputs, masks, teacher_ratio=1, loss_hint=None):
         """loss_hint (not in the reference's signature): (gold mel, lengths, eos_weight, gscale, workspace) of the speech_loss call that will
         follow on this call's outputs -- the head GEMM then computes the pre-net and stop terms and their gradient in the same launch."""
-        B, T, M = tgt.shape
-        Tk = enc_outputs.shape[1]
-        lens_q = lens_i32(tgt_lens, tgt.device)
-        lens_k = masks[1]
-        cx = self._ctx()
-        mel = tgt.detach().contiguous()
-
-        def run(tape, dummy, mem):
-            memv = _mem_in(tape, mem, B, Tk)
-            head, post = F.speech_decode(cx, tape, self, mel, lens_q, memv, lens_k, Tk, loss_hint=loss_hint)
-            return _speech_outputs(tape, head, post, B, T, M, mel.device)
-        pre, post, stop = run_segment(run, ddp_hook("speech_dec", cx.st), cx.st.dummy, enc_outputs)
+        pre, post, stop = self._decode_n([(tgt, tgt_lens, enc_outputs, masks, loss_hint)])
         return pre, post, stop, tgt_lens
 
     @on_stream("speech")
     def decode_pair(self, tgt_a, lens_a, enc_a, masks_a, hint_a, tgt_b, lens_b, enc_b, masks_b, hint_b):
         """decode_sequence(tgt_a, lens_a, enc_a, masks_a) and decode_sequence(tgt_b, lens_b, enc_b, masks_b) of two targets of ONE shape as
-        a single call: the decoder stack runs once over both (self-attention and feed-forward over 2B sequences, cross-attention per call on
-        its own memory), front ends, heads, post-net (BatchNorm statistics: first a, then b) and loss terms per call
-        (unast_amd.functional.speech_decode_pair).  Returns the two (pre, post, stop, lens) tuples of the separate calls."""
-        if tgt_a.shape != tgt_b.shape:
-            raise ValueError("decode_pair: the two targets must have one shape")
-        B, T, M = tgt_a.shape
-        Tks = (enc_a.shape[1], enc_b.shape[1])
-        lq = torch.cat([lens_i32(lens_a, tgt_a.device), lens_i32(lens_b, tgt_b.device)])
-        lens_ks = (masks_a[1], masks_b[1])
-        cx = self._ctx()
-        mels = (tgt_a.detach().contiguous(), tgt_b.detach().contiguous())
-
-        def run(tape, dummy, mem_a, mem_b):
-            mems = (_mem_in(tape, mem_a, B, Tks[0]), _mem_in(tape, mem_b, B, Tks[1]))
-            outs = F.speech_decode_pair(cx, tape, self, mels, lq, mems, lens_ks, Tks, (hint_a, hint_b))
-            res = []
-            for (head, post) in outs:
-                res += _speech_outputs(tape, head, post, B, T, M, mels[0].device)
-            return res
-        pa, qa, sa, pb, qb, sb = run_segment(run, ddp_hook("speech_dec", cx.st), cx.st.dummy, enc_a, enc_b)
+        a single call (_decode_n; the post-net's BatchNorm statistics: first a, then b).  Returns the two (pre, post, stop, lens) tuples of
+        the separate calls."""
+        pa, qa, sa, pb, qb, sb = self._decode_n([(tgt_a, lens_a, enc_a, masks_a, hint_a), (tgt_b, lens_b, enc_b, masks_b, hint_b)])
         return (pa, qa, sa, lens_a), (pb, qb, sb, lens_b)
 
     @on_stream("speech")
@@ -437,8 +393,8 @@ class SpeechTransformer(AutoEncoderNet):
         lens_k = _lens_of_pad_mask(enc_mask, Tk, tgt.device)
         cx = self._ctx()
         with torch.no_grad():
-            head, _ = F.speech_decode(cx, None, self, tgt.detach(), lens_q, Var(enc_outputs.detach().contiguous().view(B * Tk, -1)), lens_k, Tk,
-                                      shift=False, postnet=False)
+            (head, _), = F.speech_decode(cx, None, self, [tgt.detach()], lens_q, [Var(enc_outputs.detach().contiguous().view(B * Tk, -1))], [lens_k], [Tk],
+                                         shift=False, postnet=False)
         h = head.v.view(B, T, -1)[:, -1:, :]
         return h[..., :M], h[..., M:M + 1]
 

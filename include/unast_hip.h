@@ -297,6 +297,46 @@ int unast_highway_combine(const float* ht, int ld_ht, const float* x, int ld_x, 
  * b_hn [2][128]; y [B,T,256] = [forward | backward].  Nothing is saved for a backward. */
 int unast_gru_fwd(const float* xproj, const float* whh, const float* b_hn, float* y, int B, int T, int hidden, hipStream_t stream);
 
+/* --- CBHG vocoder, training (src/train_vocoder.py:85-94: train-mode forward, sum loss, loss.backward()) --- */
+/* unast_gru_fwd (src/module.py:585-587, 623-624 in train mode) that also keeps what the backward needs: saved [B,T,2,512] = per step,
+ * direction and unit (r, z, n, W_hn h + b_hn).  y is bit-equal to unast_gru_fwd's. */
+int unast_gru_fwd_train(const float* xproj, const float* whh, const float* b_hn, float* y, float* saved, int B, int T, int hidden,
+                        hipStream_t stream);
+/* Backward of that recurrence (autograd of nn.GRU under loss.backward(), src/train_vocoder.py:92).  dy, y [B,T,256]; saved as above;
+ * dx_gates [B,T,2,384] = (dr_pre, dz_pre, da), the gradient of xproj; dhn [B,T,2,128] = r * da, the n block of the hidden-side gate
+ * gradient (its r and z blocks equal dx_gates').  Weight and bias gradients are GEMMs / column sums over these (train_vocoder.py). */
+int unast_gru_bwd(const float* dy, const float* y, const float* saved, const float* whh, float* dx_gates, float* dhn, int B, int T,
+                  int hidden, hipStream_t stream);
+/* Backward of unast_maxpool_prev (src/module.py:583, 613): dx[t] = dy[t] [t == 0 or x[t-1] < x[t]] + dy[t+1] [x[t] >= x[t+1]]; a tie
+ * sends the gradient to the earlier frame, as torch's max_pool1d does.  accumulate != 0: dx += .  relu_gate != 0: the result is zeroed
+ * where x[t] <= 0 -- the backward of the ReLU that produced x (src/module.py:607), read from the stored output. */
+int unast_maxpool_prev_bwd(const float* dy, int ld_dy, const float* x, int ld_x, float* dx, int ld_dx, int B, int T, int C,
+                           int accumulate, int relu_gate, hipStream_t stream);
+/* dy = dy where y > 0, else 0, in place: backward of the ReLU behind batchnorm_proj_1 (src/module.py:616) from its stored output. */
+int unast_relu_bwd(float* dy, int ld_dy, const float* y, int ld_y, int rows, int C, hipStream_t stream);
+/* Backward of unast_highway_combine (src/module.py:524-528): dpre [rows, 2C] = gradient of ht, dx = dout * (1 - t), the direct part of
+ * the input gradient (the GEMM adds dpre W with beta = 1).  dx may be dout. */
+int unast_highway_combine_bwd(const float* dout, int ld_do, const float* ht, int ld_ht, const float* x, int ld_x, float* dpre, int ld_dp,
+                              float* dx, int ld_dx, int rows, int C, hipStream_t stream);
+/* nn.L1Loss / nn.MSELoss with reduction='sum' (src/train_vocoder.py:41-46, 91, 135-136): *loss += sum |pred - mag| (l2 = 0) or
+ * sum (pred - mag)^2 (l2 = 1) over [rows, F], accumulated in fp64 (the caller zeroes it); dpred (may be NULL) [rows, ld_dpred] = sign(diff)
+ * (sign(0) = 0) or 2 diff, zeros in columns F .. ceil4(F) - 1 when ld_dpred >= ceil4(F) (the padding the input-gradient GEMM reads). */
+int unast_sum_loss(const float* pred, int ld_pred, const float* mag, int ld_mag, float* dpred, int ld_dpred, int rows, int F, int l2,
+                   double* loss, hipStream_t stream);
+/* The parts of x under the GEMM's split-bf16 operand preparation, as dense fp32 tensors of n elements (any output may be NULL):
+ * hi = RNE_bf16(x); rest = x - hi; resid = rest - RNE_bf16(rest).  The train-mode forward of the vocoder's convolutions
+ * (src/module.py:605-617 under src/train_vocoder.py:90) is conv(hi, W) + conv(rest, W) + conv(x, resid(W)), which restores the
+ * products one three-term launch drops. */
+int unast_split_parts(const float* x, float* hi, float* rest, float* resid, int64_t n, hipStream_t stream);
+/* Input and weight gradients of unast_conv_fwd's convolution for 1..16 taps (autograd of nn.Conv1d, src/module.py:553-577 under
+ * src/train_vocoder.py:92).  dX[(b,t)][c] (+)= sum_{j,o} dY[b, t - j + pad_left, o] Wp[o][j][c] (beta = 0 / 1);
+ * dWp[o][j][c] += sum_{b,t} dY[b,t,o] X[b, t + j - pad_left, c], db[o] += sum dY (db may be NULL).  All operands may be column slices
+ * (row strides); Wp / dWp are dense [Cout][taps][Cin].  With taps = 5 these are the launches unast_gemm makes for its conv forms. */
+int unast_conv_dgrad(int nsplit, const float* dY, int lddy, const float* Wp, float* dX, int lddx, int B, int T, int Cin, int Cout,
+                     int taps, int pad_left, int beta, hipStream_t stream);
+int unast_conv_wgrad(int nsplit, const float* dY, int lddy, const float* X, int ldx, float* dWp, int B, int T, int Cin, int Cout,
+                     int taps, int pad_left, float* db, int splitk, float* ws, int64_t ws_floats, hipStream_t stream);
+
 /* Registers a 4-byte counter in device memory that every dropout / noise kernel adds to its stream id (NULL = none).  Launches
  * replayed from a captured HIP graph carry fixed (seed, stream_id) arguments; the generation loop of infer_sequence
  * (src/network.py:219-252, 455-481: fresh dropout masks at every decoded position when the model is in training mode)

@@ -632,7 +632,7 @@ static void launch_split(const GemmParams& p, int nsplit, int wn, int flags, dim
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// conv_ks: taps of the implicit-conv forms (unast_gemm: 5; unast_conv_fwd: 1..16).
+// conv_ks: taps of the implicit-conv forms (unast_gemm: 5; unast_conv_fwd / unast_conv_dgrad / unast_conv_wgrad: 1..16).
 static int gemm_run(int a_mode, int b_mode, int nsplit,
                     const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     int M, int N, int K, int kb_valid,
@@ -702,8 +702,8 @@ static int gemm_run(int a_mode, int b_mode, int nsplit,
         }
     }
     if (a_mode == OP_KC_CONV) UNAST_REQUIRE((conv_ca & 3) == 0 && K == conv_ks * conv_ca && M % p.T == 0, "unast_gemm: bad conv A geometry");
-    if (b_mode == OP_RC_CONV_DGRAD) UNAST_REQUIRE(K == 5 * conv_cb, "unast_gemm: bad conv dgrad geometry");
-    if (b_mode == OP_RC_CONV_WGRAD) UNAST_REQUIRE((conv_cb & 3) == 0 && N == 5 * conv_cb && K % p.T == 0, "unast_gemm: bad conv wgrad geometry");
+    if (b_mode == OP_RC_CONV_DGRAD) UNAST_REQUIRE(K == conv_ks * conv_cb, "unast_gemm: bad conv dgrad geometry");
+    if (b_mode == OP_RC_CONV_WGRAD) UNAST_REQUIRE((conv_cb & 3) == 0 && N == conv_ks * conv_cb && K % p.T == 0, "unast_gemm: bad conv wgrad geometry");
     p.nsplitk = splitk;
     // interior-only fast path (FLAGS bit 0): see gemm_kernel
     int flags = b_presplit ? 2 : 0;
@@ -756,6 +756,32 @@ extern "C" int unast_conv_fwd(int nsplit, const float* X, int ldx, const float* 
     UNAST_REQUIRE((long long)B * T <= 0x7FFFFFFF && (long long)taps * Cin <= 0x7FFFFFFF, "unast_conv_fwd: problem too large");
     return gemm_run(OP_KC_CONV, OP_KC, nsplit, X, ldx, Wp, taps * Cin, Y, ldy, B * T, Cout, taps * Cin, 0, T, Cin, 0, pad_left, taps,
                     bias, R, ldr, nullptr, 0, 1.f, 1.f, 0, act, 0.f, 0u, 0u, 1, nullptr, 0, nullptr, 0, 0, 0, nullptr, stream);
+}
+
+// Input gradient of that convolution: dX[(b,t)][c] (+)= sum_{j,o} dY[b, t - j + pad_left, o] Wp[o][j][c] -- the launch unast_gemm makes for
+// its conv dgrad form (a_mode 1, b_mode 3) at taps = 5, with the tap count free.
+extern "C" int unast_conv_dgrad(int nsplit, const float* dY, int lddy, const float* Wp, float* dX, int lddx, int B, int T, int Cin, int Cout,
+                                int taps, int pad_left, int beta, hipStream_t stream) {
+    UNAST_REQUIRE(taps >= 1 && taps <= 16, "unast_conv_dgrad: 1..16 taps (got %d)", taps);
+    UNAST_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0 && (Cin & 3) == 0 && (Cout & 3) == 0,
+                  "unast_conv_dgrad: bad dims B=%d T=%d Cin=%d Cout=%d (both %% 4 == 0)", B, T, Cin, Cout);
+    UNAST_REQUIRE(pad_left >= 0 && pad_left < taps, "unast_conv_dgrad: pad_left must be in [0, taps)");
+    UNAST_REQUIRE(lddy >= Cout && lddx >= Cin && (beta == 0 || beta == 1), "unast_conv_dgrad: row strides shorter than the rows, or beta not 0 / 1");
+    UNAST_REQUIRE((long long)B * T <= 0x7FFFFFFF && (long long)taps * Cout <= 0x7FFFFFFF, "unast_conv_dgrad: problem too large");
+    return gemm_run(OP_KC_CONV, OP_RC_CONV_DGRAD, nsplit, dY, lddy, Wp, 4, dX, lddx, B * T, Cin, taps * Cout, 0, T, Cout, Cout, taps - 1 - pad_left, taps,
+                    nullptr, nullptr, 0, nullptr, 0, 1.f, 1.f, beta, 0, 0.f, 0u, 0u, 1, nullptr, 0, nullptr, 0, 0, 0, nullptr, stream);
+}
+
+// Weight gradient: dWp[o][j][c] += sum_{b,t} dY[b,t,o] X[b, t + j - pad_left, c]; db[o] += sum dY if db != NULL.  splitk / ws as unast_gemm.
+extern "C" int unast_conv_wgrad(int nsplit, const float* dY, int lddy, const float* X, int ldx, float* dWp, int B, int T, int Cin, int Cout,
+                                int taps, int pad_left, float* db, int splitk, float* ws, int64_t ws_floats, hipStream_t stream) {
+    UNAST_REQUIRE(taps >= 1 && taps <= 16, "unast_conv_wgrad: 1..16 taps (got %d)", taps);
+    UNAST_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0 && (Cin & 3) == 0, "unast_conv_wgrad: bad dims B=%d T=%d Cin=%d Cout=%d (Cin %% 4 == 0)", B, T, Cin, Cout);
+    UNAST_REQUIRE(pad_left >= 0 && pad_left < taps, "unast_conv_wgrad: pad_left must be in [0, taps)");
+    UNAST_REQUIRE(lddy >= ((Cout + 3) & ~3) && ldx >= Cin, "unast_conv_wgrad: row strides shorter than the rows");
+    UNAST_REQUIRE((long long)B * T <= 0x7FFFFFFF && (long long)taps * Cin <= 0x7FFFFFFF, "unast_conv_wgrad: problem too large");
+    return gemm_run(OP_RC, OP_RC_CONV_WGRAD, nsplit, dY, lddy, X, ldx, dWp, taps * Cin, Cout, taps * Cin, B * T, 0, T, 0, Cin, pad_left, taps,
+                    nullptr, nullptr, 0, nullptr, 0, 1.f, 1.f, 1, 0, 0.f, 0u, 0u, splitk, ws, ws_floats, db, 0, 0, 0, nullptr, stream);
 }
 
 // Host side of the grouped weight-gradient launch.  items[i] = {A = dY_i [tokens][M_i] (row stride lda), B = X_i [tokens][N_i],

@@ -6,7 +6,8 @@ Public surface kept:
   TextTransformer / SpeechTransformer(args): encode, decode_sequence, forward, preprocess
   LSTMDiscriminator(d_in, hidden, out=1, bidirectional=False, num_layers=1, dropout=.2, relu=.2).forward(out, out_len)
   Discriminator(enc_dim, hidden=1024, out_classes=1, dropout=.2, relu=.2).forward(enc_output)
-  Vocoder(num_mels, hidden_size, num_fft).forward(mel) -- eval mode under torch.no_grad() only (unast_amd.vocoder) -- and make_mags
+  Vocoder(num_mels, hidden_size, num_fft).forward(mel) -- eval mode under torch.no_grad() only (unast_amd.vocoder) -- and make_mags;
+  its training step vocoder_step / valid_loss / FlatAdamW / vocoder_train_step (unast_amd.train_vocoder; src/train_vocoder.py:85-100)
 `state_dict()` keys/shapes equal the reference's (unast_amd.spec).  The `masks` tuple returned by encode() is opaque
 to callers in the reference (only passed back into decode_sequence); here it carries int32 lengths instead of bool
 mask tensors — the kernels test `t < len[b]` themselves (no B x T host loop, cf. src/utils.py:77-83).
@@ -24,6 +25,7 @@ from .module import (SpeechPrenet, SpeechPostnet, TextPrenet, TextPostnet, Posit
 from .spec import state_dict_spec  # noqa: F401  (re-export)
 from .utils import PAD_IDX, SOS_IDX, EOS_IDX, lens_i32, next_seed  # noqa: F401
 from .vocoder import Vocoder, make_mags  # noqa: F401  (src/network.py:627-655, src/inf_vocoder.py:56-64; eval forward only)
+from .train_vocoder import FlatAdamW, train_step as vocoder_train_step, valid_loss, vocoder_step  # noqa: F401,E402  (src/train_vocoder.py:85-100, 135-136)
 
 _HP_KEYS = ("num_mels", "s_pre_hid", "s_pre_drop", "s_post_drop", "t_emb_dim", "t_pre_drop", "t_post_drop", "hidden", "e_in",
             "e_drop", "d_drop", "num_layers", "nhead", "ffn_dim")

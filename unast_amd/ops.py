@@ -839,6 +839,145 @@ def gru_fwd(xproj, whh, b_hn, y):
     return y
 
 
+# ---- CBHG vocoder (training) -------------------------------------------------------------------------------
+def _btc(t, B, T):
+    """[B,T,C] with unit column stride and dense batch strides (a column slice of a wider buffer qualifies)."""
+    return t.dim() == 3 and t.shape[0] == B and t.shape[1] == T and t.stride(2) == 1 and t.stride(0) == T * t.stride(1)
+
+
+def gru_fwd_train(xproj, whh, b_hn, y, saved):
+    """gru_fwd that also writes saved [B,T,2,512] = (r, z, n, W_hn h + b_hn) per step, direction and unit for gru_bwd."""
+    B, T = xproj.shape[0], xproj.shape[1]
+    if not (xproj.is_contiguous() and whh.is_contiguous() and b_hn.is_contiguous() and y.is_contiguous() and saved.is_contiguous()
+            and xproj.dim() == 3 and xproj.shape[2] == 768 and tuple(whh.shape) == (2, 384, 128) and tuple(b_hn.shape) == (2, 128)
+            and tuple(y.shape) == (B, T, 256) and tuple(saved.shape) == (B, T, 2, 512)):
+        raise ValueError("gru_fwd_train: contiguous xproj [B,T,768], whh [2,384,128], b_hn [2,128], y [B,T,256], saved [B,T,2,512]")
+    for t, n in ((xproj, "xproj"), (whh, "whh"), (b_hn, "b_hn"), (y, "y"), (saved, "saved")):
+        _f32(t, n)
+    check(lib().unast_gru_fwd_train(_p(xproj), _p(whh), _p(b_hn), _p(y), _p(saved), B, T, 128, _stream()), "unast_gru_fwd_train")
+    return y
+
+
+def gru_bwd(dy, y, saved, whh, dx_gates, dhn):
+    """dy, y [B,T,256]; saved [B,T,2,512] from gru_fwd_train; whh [2,384,128] -> dx_gates [B,T,2,384] = (dr_pre, dz_pre, da), the gradient
+    of xproj, and dhn [B,T,2,128] = r * da."""
+    B, T = y.shape[0], y.shape[1]
+    if not (dy.is_contiguous() and y.is_contiguous() and saved.is_contiguous() and whh.is_contiguous() and dx_gates.is_contiguous()
+            and dhn.is_contiguous() and y.dim() == 3 and y.shape[2] == 256 and dy.shape == y.shape and tuple(saved.shape) == (B, T, 2, 512)
+            and tuple(whh.shape) == (2, 384, 128) and tuple(dx_gates.shape) == (B, T, 2, 384) and tuple(dhn.shape) == (B, T, 2, 128)):
+        raise ValueError("gru_bwd: contiguous dy, y [B,T,256], saved [B,T,2,512], whh [2,384,128], dx_gates [B,T,2,384], dhn [B,T,2,128]")
+    for t, n in ((dy, "dy"), (y, "y"), (saved, "saved"), (whh, "whh"), (dx_gates, "dx_gates"), (dhn, "dhn")):
+        _f32(t, n)
+    check(lib().unast_gru_bwd(_p(dy), _p(y), _p(saved), _p(whh), _p(dx_gates), _p(dhn), B, T, 128, _stream()), "unast_gru_bwd")
+    return dx_gates, dhn
+
+
+def maxpool_prev_bwd(dy3d, x3d, dx3d, accumulate=False, relu_gate=False):
+    """Backward of maxpool_prev (ties to the earlier frame); accumulate: dx += ; relu_gate: zero where x <= 0."""
+    if x3d.dim() != 3:
+        raise ValueError("maxpool_prev_bwd: [B,T,C] operands")
+    B, T, C = x3d.shape
+    if not (dy3d.shape == x3d.shape and dx3d.shape == x3d.shape and _btc(dy3d, B, T) and _btc(x3d, B, T) and _btc(dx3d, B, T)):
+        raise ValueError("maxpool_prev_bwd: [B,T,C] operands of one shape with dense batch strides")
+    _f32(dy3d, "dy"), _f32(x3d, "x"), _f32(dx3d, "dx")
+    check(lib().unast_maxpool_prev_bwd(_p(dy3d), dy3d.stride(1), _p(x3d), x3d.stride(1), _p(dx3d), dx3d.stride(1), B, T, C,
+                                       int(bool(accumulate)), int(bool(relu_gate)), _stream()), "unast_maxpool_prev_bwd")
+    return dx3d
+
+
+def relu_bwd(dy2d, y2d):
+    """dy = dy where y > 0 else 0, in place."""
+    if not (dy2d.dim() == 2 and dy2d.shape == y2d.shape and dy2d.stride(1) == 1 and y2d.stride(1) == 1):
+        raise ValueError("relu_bwd: dy and y [rows, C], unit column strides")
+    _f32(dy2d, "dy"), _f32(y2d, "y")
+    check(lib().unast_relu_bwd(_p(dy2d), dy2d.stride(0), _p(y2d), y2d.stride(0), dy2d.shape[0], dy2d.shape[1], _stream()), "unast_relu_bwd")
+    return dy2d
+
+
+def highway_combine_bwd(dout, ht, x, dpre, dx):
+    """Backward of highway_combine: dpre [rows, 2C] = gradient of ht, dx = dout * (1 - t) (dx may be dout)."""
+    if x.dim() != 2:
+        raise ValueError("highway_combine_bwd: x [rows, C]")
+    rows, C = x.shape
+    if not (tuple(ht.shape) == (rows, 2 * C) and tuple(dpre.shape) == (rows, 2 * C) and dout.shape == x.shape and dx.shape == x.shape
+            and all(t.stride(1) == 1 for t in (dout, ht, x, dpre, dx))):
+        raise ValueError("highway_combine_bwd: ht and dpre [rows, 2C], dout, x and dx [rows, C], unit column strides")
+    for t, n in ((dout, "dout"), (ht, "ht"), (x, "x"), (dpre, "dpre"), (dx, "dx")):
+        _f32(t, n)
+    check(lib().unast_highway_combine_bwd(_p(dout), dout.stride(0), _p(ht), ht.stride(0), _p(x), x.stride(0), _p(dpre), dpre.stride(0),
+                                          _p(dx), dx.stride(0), rows, C, _stream()), "unast_highway_combine_bwd")
+    return dpre, dx
+
+
+def sum_loss(pred2d, mag2d, dpred, l2, loss):
+    """loss (float64 scalar tensor, zeroed by the caller) += sum |pred - mag| or sum (pred - mag)^2 over [rows, F]; dpred (or None)
+    [rows, F] receives sign(diff) / 2 diff, and zeros in columns F .. ceil4(F) - 1 when its row stride has room for them."""
+    if not (pred2d.dim() == 2 and mag2d.shape == pred2d.shape and pred2d.stride(1) == 1 and mag2d.stride(1) == 1
+            and (dpred is None or (dpred.dim() == 2 and dpred.shape == pred2d.shape and dpred.stride(1) == 1 and dpred.stride(0) >= pred2d.shape[1]))):
+        raise ValueError("sum_loss: pred, mag and dpred [rows, F] with unit column strides")
+    if loss.dtype is not torch.float64 or loss.numel() != 1:
+        raise ValueError("sum_loss: the loss accumulator is one float64")
+    _f32(pred2d, "pred"), _f32(mag2d, "mag"), _f32(dpred, "dpred")
+    if not loss.is_cuda:
+        raise TypeError("sum_loss: the loss accumulator must live on the GPU")
+    rows, F = pred2d.shape
+    check(lib().unast_sum_loss(_p(pred2d), pred2d.stride(0), _p(mag2d), mag2d.stride(0), _p(dpred), dpred.stride(0) if dpred is not None else 0,
+                               rows, F, int(bool(l2)), _p(loss), _stream()), "unast_sum_loss")
+    return loss
+
+
+def split_parts(x, hi=None, rest=None, resid=None):
+    """The parts of x under the GEMM's split-bf16 operand preparation: hi = RNE_bf16(x), rest = x - hi, resid = rest - RNE_bf16(rest)
+    (contiguous fp32 tensors of x's size; any of them may be None)."""
+    outs = [t for t in (hi, rest, resid) if t is not None]
+    if not outs or not x.is_contiguous() or any(not t.is_contiguous() or t.numel() != x.numel() for t in outs):
+        raise ValueError("split_parts: contiguous tensors of one size, at least one output")
+    for t, n in ((x, "x"), (hi, "hi"), (rest, "rest"), (resid, "resid")):
+        _f32(t, n)
+    check(lib().unast_split_parts(_p(x), _p(hi), _p(rest), _p(resid), x.numel(), _stream()), "unast_split_parts")
+
+
+def _conv_grad_layout(name, dy3d, Wp, x3d, pad_left):
+    if dy3d.dim() != 3 or x3d.dim() != 3 or Wp.dim() != 3:
+        raise ValueError("%s: dy [B,T,Cout], x / dx [B,T,Cin], Wp [Cout,taps,Cin]" % name)
+    B, T, Cout = dy3d.shape
+    Cin = x3d.shape[2]
+    taps = Wp.shape[1]
+    if not (Wp.is_contiguous() and tuple(Wp.shape) == (Cout, taps, Cin) and 1 <= taps <= 16 and 0 <= pad_left < taps and _btc(dy3d, B, T) and _btc(x3d, B, T)
+            and Cin % 4 == 0 and dy3d.stride(1) % 4 == 0 and x3d.stride(1) % 4 == 0):
+        raise ValueError("%s: tap-major contiguous weights [Cout,1..16,Cin], [B,T,C] operands with dense batch strides, strides and Cin "
+                         "multiples of 4" % name)
+    for t, n in ((dy3d, "dy"), (Wp, "W"), (x3d, "x")):
+        _f32(t, n)
+    return B, T, Cin, Cout, taps
+
+
+def conv_taps_dgrad(dy3d, Wp, dx3d, pad_left, beta=0):
+    """Input gradient of conv_taps_fwd: dx[b,t,c] (+)= sum_{j,o} dy[b, t - j + pad_left, o] Wp[o,j,c]; operands may be column slices."""
+    B, T, Cin, Cout, taps = _conv_grad_layout("conv_taps_dgrad", dy3d, Wp, dx3d, pad_left)
+    if Cout % 4 != 0 or beta not in (0, 1):
+        raise ValueError("conv_taps_dgrad: Cout %% 4 == 0 and beta 0 or 1")
+    check(lib().unast_conv_dgrad(config.NSPLIT, _p(dy3d), dy3d.stride(1), _p(Wp), _p(dx3d), dx3d.stride(1), B, T, Cin, Cout, taps, pad_left,
+                                 int(beta), _stream()), "unast_conv_dgrad")
+    return dx3d
+
+
+def conv_taps_wgrad(dy3d, x3d, dWp, pad_left, db=None):
+    """dWp[o,j,c] += sum_{b,t} dy[b,t,o] x[b, t + j - pad_left, c]; db[o] += sum dy.  On the current stream."""
+    if db is not None and not (db.numel() == dy3d.shape[-1] and db.is_contiguous()):
+        raise ValueError("conv_taps_wgrad: db [Cout]")
+    B, T, Cin, Cout, taps = _conv_grad_layout("conv_taps_wgrad", dy3d, dWp, x3d, pad_left)
+    _f32(db, "db")
+    sk = _splitk_for(Cout, taps * Cin, B * T)
+    ws, ws_n = None, 0
+    if sk > 1:
+        ws_n = sk * Cout * taps * Cin
+        ws = torch.empty(ws_n, dtype=torch.float32, device=dWp.device)
+    check(lib().unast_conv_wgrad(config.NSPLIT, _p(dy3d), dy3d.stride(1), _p(x3d), x3d.stride(1), _p(dWp), B, T, Cin, Cout, taps, pad_left,
+                                 _p(db), sk, _p(ws), ws_n, _stream()), "unast_conv_wgrad")
+    return dWp
+
+
 # ---- optimizer ---------------------------------------------------------------------------------------------
 _MSE_WS = {}
 

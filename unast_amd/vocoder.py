@@ -8,7 +8,8 @@ edits): conv weights tap-major [Cout,k,Cin] with the eval BatchNorm folded in, e
 [512,256] matrix, each GRU layer's weight_ih of both directions as one [768,256] matrix.
 
 Supported: Vocoder(num_mels, 256, num_fft) with num_mels a multiple of 4 (the reference builds Vocoder(80, 256, 2048)); eval mode under
-torch.no_grad() only.  Vocoder training and Griffin-Lim / spectrogram2wav are not part of this package.
+torch.no_grad() only.  Training has its own entry point, unast_amd.train_vocoder.vocoder_step (this forward keeps refusing train mode);
+Griffin-Lim / spectrogram2wav are not part of this package.
 """
 import torch
 import torch.nn as nn
@@ -141,7 +142,7 @@ class Vocoder(nn.Module):
     def _run(self, mel, taps):
         if self.training:
             raise NotImplementedError("Vocoder.forward is the eval forward only (BatchNorm running statistics, no backward); call "
-                                      "model.eval() and run under torch.no_grad() -- vocoder training is not part of this package")
+                                      "model.eval() and run under torch.no_grad() -- the train-mode step is unast_amd.train_vocoder.vocoder_step")
         if torch.is_grad_enabled():
             raise NotImplementedError("Vocoder.forward has no backward on this path; run it under torch.no_grad()")
         if mel.dim() != 3 or mel.shape[2] != self.num_mels or not mel.is_cuda or mel.dtype is not _F32:

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import dropout_mirror as M
+from tests import ragged_ref
 
 pytestmark = pytest.mark.gpu
 D = torch.device("cuda:0")
@@ -41,18 +42,8 @@ def assert_zero_pattern(got, kp, pre=None):
 # ---- attention ---------------------------------------------------------------------------------------------
 def attention_ref(q, k, v, lens_k, causal, H, drop):
     """fp64 attention with dropout on the normalised probabilities (drop: [B, H, Tq, Tk] factor); LSE is that of the undropped scores."""
-    B, Tq, E = q.shape
-    Tk = k.shape[1]
-    qh = q.view(B, Tq, H, 64).transpose(1, 2) / 8.0
-    kh = k.view(B, Tk, H, 64).transpose(1, 2)
-    vh = v.view(B, Tk, H, 64).transpose(1, 2)
-    s = qh @ kh.transpose(-1, -2)
-    neg = ~(torch.arange(Tk)[None, :] < lens_k[:, None])[:, None, None, :]
-    if causal:
-        neg = neg | (torch.arange(Tk)[None, :] > torch.arange(Tq)[:, None])[None, None]
-    s = s.masked_fill(neg, float("-inf"))
-    p = torch.softmax(s, -1) * drop
-    return (p @ vh).transpose(1, 2).reshape(B, Tq, E), torch.logsumexp(s, -1), neg
+    o, lse = ragged_ref.attention_ref(q, k, v, lens_k, causal, H, drop)
+    return o, lse, None
 
 
 @pytest.fixture

@@ -318,6 +318,37 @@ def test_embed_posenc_rowmask():
     assert torch.allclose(ad.cpu(), a + b)
 
 
+def test_shift_frames_sum2_add_strided_scale_inplace():
+    """Element-wise entry points of the train step, exact (one fp32 operation per element, the same on the host)."""
+    from unast_amd import ops
+    g = torch.Generator().manual_seed(6)
+    # shift_frames: the all-zero go frame at t = 0, frame t - 1 at t; a single-frame sequence is the go frame alone
+    for B, T, M in ((3, 37, 80), (2, 1, 80), (5, 9, 4)):
+        mel = torch.randn(B, T, M, generator=g)
+        out = torch.full((B, T, M), float("nan"), device=D)
+        ops.shift_frames(mel.to(D), out)
+        assert bool((out[:, 0] == 0).all()) and torch.equal(out[:, 1:].cpu(), mel[:, :-1])
+    # sum2: a size that is no multiple of 4 (the scalar tail after the float4 body), two addends and one
+    a, b = torch.randn(1001, generator=g), torch.randn(1001, generator=g)
+    dst = torch.full((1001,), float("nan"), device=D)
+    ops.sum2(dst, a.to(D), b.to(D))
+    assert torch.equal(dst.cpu(), a + b)
+    dst.fill_(float("nan"))
+    ops.sum2(dst, a.to(D), None)
+    assert torch.equal(dst.cpu(), a)
+    # add_strided: different row pitches, the columns past `cols` of both untouched / unread, more than one workgroup
+    rows, cols = 300, 5
+    d0, s0 = torch.randn(rows, 12, generator=g), torch.randn(rows, 8, generator=g)
+    s0[:, cols:] = float("nan")
+    dd = d0.to(D)
+    ops.add_strided(dd, s0.to(D), cols)
+    assert torch.equal(dd[:, :cols].cpu(), d0[:, :cols] + s0[:, :cols]) and torch.equal(dd[:, cols:].cpu(), d0[:, cols:])
+    # scale_inplace
+    ad = a.to(D)
+    ops.scale_inplace(ad, 0.37)
+    assert torch.equal(ad.cpu(), a * torch.tensor(0.37))
+
+
 def test_losses_match_oracle():
     from unast_amd import ops
     from oracle import unast_ref as R

@@ -53,10 +53,10 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, bf16x8_
     lo = __builtin_bit_cast(bf16x8_t, l);
 }
 
-// 8 consecutive operand elements at `src` -> hi/lo fragments: fp32 values (optionally scaled) are split here; pre-split data
-// ([hi x4 | lo x4] per 16-byte chunk) is only re-packed.  `ok` false -> zeros.
+// 8 consecutive operand elements at `src` -> hi/lo fragments: fp32 values are split here, as unast_split_f32 splits them; pre-split
+// data ([hi x4 | lo x4] per 16-byte chunk) is only re-packed.  `ok` false -> zeros.
 template <int NSPLIT>
-__device__ __forceinline__ void load_frag8(const float* __restrict__ src, bool ok, bool split_in, float pre_scale, bf16x8_t& hi, bf16x8_t& lo) {
+__device__ __forceinline__ void load_frag8(const float* __restrict__ src, bool ok, bool split_in, bf16x8_t& hi, bf16x8_t& lo) {
     float4 a = make_float4(0, 0, 0, 0), c = a;
     if (ok) {
         a = *reinterpret_cast<const float4*>(src);
@@ -68,7 +68,6 @@ __device__ __forceinline__ void load_frag8(const float* __restrict__ src, bool o
         hi = __builtin_bit_cast(bf16x8_t, h);
         lo = __builtin_bit_cast(bf16x8_t, l);
     } else {
-        a.x *= pre_scale; a.y *= pre_scale; a.z *= pre_scale; a.w *= pre_scale; c.x *= pre_scale; c.y *= pre_scale; c.z *= pre_scale; c.w *= pre_scale;
         split8<NSPLIT>(a, c, hi, lo);
     }
 }
@@ -204,10 +203,11 @@ __global__ __launch_bounds__(128 * (4 / QS), (QS == 1 ? 4 : 2)) void attn_q_kern
     const float sc = p.scale * LOG2E;
 
     // per-wave query-side operand fragments: lane holds X[q = q0+16qs+l15][d = 32kst+8g..+7]
-    // Scores are wanted in log2 units: fp32 Q is multiplied by scale*log2(e) before it is split; pre-split Q cannot be, so
-    // there the factor rides in the exponent's fma (ssc) instead -- the same instruction count either way.
+    // Scores are wanted in log2 units: the factor scale*log2(e) rides in the exponent's fma.  (fp32 Q is split as it is, never
+    // scaled first: every kernel of the forward and the backward, and the pre-split format, then see the SAME hi/lo parts of an
+    // operand -- with Q * scale*log2(e) split here and Q itself in the dK / dV kernel, the two forms of the backward disagreed
+    // on a short key set by more than their bound, where no sum over many keys averages the 2^-17 differences out.)
     const bool split_in = p.qkv_split != 0;
-    const float ssc = split_in ? sc : 1.f;
     bf16x8_t qf[QS][2][PARTS], dof[QS][2][PARTS];
     float lse2[QS], delta[QS];
 #pragma unroll
@@ -219,11 +219,11 @@ __global__ __launch_bounds__(128 * (4 / QS), (QS == 1 ? 4 : 2)) void attn_q_kern
 #pragma unroll
         for (int kst = 0; kst < 2; ++kst) {
             bf16x8_t hi, lo;
-            load_frag8<NSPLIT>(Qb + (size_t)q * p.ldq + 32 * kst + 8 * g, ok, split_in, sc, hi, lo);
+            load_frag8<NSPLIT>(Qb + (size_t)q * p.ldq + 32 * kst + 8 * g, ok, split_in, hi, lo);
             qf[qs][kst][0] = hi;
             if (PARTS == 2) qf[qs][kst][PARTS - 1] = lo;
             if (MODE == 1) {
-                load_frag8<NSPLIT>(p.dO + ((size_t)b * p.Tq + q) * p.lddo + h * HD + 32 * kst + 8 * g, ok, split_in, 1.f, hi, lo);
+                load_frag8<NSPLIT>(p.dO + ((size_t)b * p.Tq + q) * p.lddo + h * HD + 32 * kst + 8 * g, ok, split_in, hi, lo);
                 dof[qs][kst][0] = hi;
                 if (PARTS == 2) dof[qs][kst][PARTS - 1] = lo;
             }
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(128 * (4 / QS), (QS == 1 ? 4 : 2)) void attn_q_kern
                             tmax = fmaxf(tmax, v);
                         }
                     tmax = rows4_max(tmax);
-                    const float mnew = fmaxf(m[qs], tmax * ssc);
+                    const float mnew = fmaxf(m[qs], tmax * sc);
                     const float alpha = __builtin_amdgcn_exp2f(m[qs] - mnew);
                     m[qs] = mnew;
                     mref = mnew;
@@ -339,11 +339,11 @@ __global__ __launch_bounds__(128 * (4 / QS), (QS == 1 ? 4 : 2)) void attn_q_kern
                         float pv;
                         if (MODE == 0) {
                             const float v = s[ks][qs][r];
-                            pv = __builtin_amdgcn_exp2f(__builtin_fmaf(v, ssc, -mref));      // masked entries: exp2(-1e30 * ssc - m) = 0
+                            pv = __builtin_amdgcn_exp2f(__builtin_fmaf(v, sc, -mref));      // masked entries: exp2(-1e30 * sc - m) = 0
                             rs += pv;
                             s[ks][qs][r] = keep ? pv : 0.f;          // 1/(1-p) is applied once, in the epilogue's normalisation
                         } else {
-                            pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[ks][qs][r], ssc, -mref));
+                            pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[ks][qs][r], sc, -mref));
                             if (MASKED) {
                                 const int key = key0 + r;
                                 const bool valid = key < klen && (!p.causal || key <= q) && q < p.Tq;
@@ -496,7 +496,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
     const float* Vb = p.V + (size_t)b * p.Tk * p.ldv + h * HD;
     const float sc = p.scale * LOG2E;
     const bool split_in = p.qkv_split != 0;
-    const float ssc = split_in ? sc : 1.f;
     const int q = q0 + n;
     const bool qok = q < p.Tq;
 
@@ -504,7 +503,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
 #pragma unroll
     for (int kst = 0; kst < 4; ++kst) {
         bf16x8_t fh, fl;
-        load_frag8<NSPLIT>(Qb + (size_t)q * p.ldq + 16 * kst + 8 * hi, qok, split_in, sc, fh, fl);
+        load_frag8<NSPLIT>(Qb + (size_t)q * p.ldq + 16 * kst + 8 * hi, qok, split_in, fh, fl);
         qf[kst][0] = fh;
         if (PARTS == 2) qf[kst][PARTS - 1] = fl;
     }
@@ -585,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
                     }
                     tmax = fmaxf(tmax, v);
                 }
-            const float ts = half_max(tmax) * ssc;
+            const float ts = half_max(tmax) * sc;
             // The running maximum follows a query's tile maximum only once that exceeds it by more than ATTN_DEFER_MAX (P <= 2^8 meanwhile:
             // exact in fp32 and in the hi/lo split), so alpha is exactly 1 in most iterations.  Branch-free on purpose: with the rescaling
             // pass under a wave-uniform branch the compiler kept three copies of the 32 output accumulators (94 v_mov_b64 per iteration).
@@ -610,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         const bool keep = !p.drop_thresh || (e ? rng_keep_hi(hh, p.drop_thresh) : rng_keep_lo(hh, p.drop_thresh));
-                        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t2][i + e], ssc, -m));      // masked entries: exp2(-1e30 * ssc - m) = 0
+                        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t2][i + e], sc, -m));      // masked entries: exp2(-1e30 * sc - m) = 0
                         rs += pv;
                         s[t2][i + e] = keep ? pv : 0.f;
                     }
@@ -731,10 +730,10 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(const AttnParams p) {
         for (int kst = 0; kst < 2; ++kst) {
             bf16x8_t hi, lo;
             if (!FUSE_DQ) {      // (one-pass form: the K fragments are re-read from the workgroup's K image every iteration, see below)
-                load_frag8<NSPLIT>(Kb + (size_t)key * p.ldk + 32 * kst + 8 * g, ok, split_in, 1.f, hi, lo);
+                load_frag8<NSPLIT>(Kb + (size_t)key * p.ldk + 32 * kst + 8 * g, ok, split_in, hi, lo);
                 kf[ks][kst][0] = hi; if (PARTS == 2) kf[ks][kst][PARTS - 1] = lo;
             }
-            load_frag8<NSPLIT>(Vb + (size_t)key * p.ldv + 32 * kst + 8 * g, ok, split_in, 1.f, hi, lo);
+            load_frag8<NSPLIT>(Vb + (size_t)key * p.ldv + 32 * kst + 8 * g, ok, split_in, hi, lo);
             vf[ks][kst][0] = hi; if (PARTS == 2) vf[ks][kst][PARTS - 1] = lo;
         }
     }
@@ -969,8 +968,13 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
         if (h < H) {
             const int c = h * HD + (lane & 15) * 4;
             float4 a = *reinterpret_cast<const float4*>(dO + (size_t)row * lddo + c);
-            if (do_split) {         // [hi x4 | lo x4] -> the 4 values (hi + lo, to the ~16 bits the products see anyway)
-                const uint32_t h0 = __float_as_uint(a.x), h1 = __float_as_uint(a.y), l0 = __float_as_uint(a.z), l1 = __float_as_uint(a.w);
+            {       // hi + lo: the ~16 bits of dO that the products of the backward see.  fp32 dO is split here for that, [hi x4 | lo x4]
+                    // is unpacked: dP = dO . V then cancels against Delta = dO . O on a row with one visible key (O = V, dS = 0 exactly)
+                    // to the products' own error, not to the 2^-17 |dO| |V| that the full-precision dO left there.
+                u32x2 sh = {0u, 0u}, sl = sh;
+                if (!do_split) split4<3>(a, sh, sl);
+                const uint32_t h0 = do_split ? __float_as_uint(a.x) : sh[0], h1 = do_split ? __float_as_uint(a.y) : sh[1];
+                const uint32_t l0 = do_split ? __float_as_uint(a.z) : sl[0], l1 = do_split ? __float_as_uint(a.w) : sl[1];
                 a.x = __uint_as_float(h0 << 16) + __uint_as_float(l0 << 16);
                 a.y = __uint_as_float(h0 & 0xFFFF0000u) + __uint_as_float(l0 & 0xFFFF0000u);
                 a.z = __uint_as_float(h1 << 16) + __uint_as_float(l1 << 16);

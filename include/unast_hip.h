@@ -272,6 +272,48 @@ int unast_lstm_fwd(const float* xproj, const float* whh, const float* b_ih, cons
                    int64_t bias_dir_stride, hipStream_t stream);
 int unast_lstm_bwd(const float* dy, const float* dhfinal, const float* whh, const float* gates, const float* cs, const int* lens,
                    float* dgates, int Bd, int T, int ndir, int hidden, int64_t whh_dir_stride, hipStream_t stream);
+/* ---- RNN model family, eval path (csrc/rnn.hip; TextRNN / SpeechRNN, src/network.py:279-402, 503-624) at hidden = 256 ----------
+ * unast_lstm_seq_fwd: recurrent part of one packed nn.LSTM layer (src/module.py:306, 315-317: pack_padded_sequence, nn.LSTM,
+ * pad_packed_sequence), gate order i,f,g,o, forward only (nothing is saved for a backward).  xproj [B,T,ndir*1024] = X W_ih^T (no bias),
+ * b_ih / b_hh [ndir*1024], lens [B] (clamped to 0..T).  The reverse direction starts at lens[b]-1.  y [B,T,ndir*256] (rows t >= lens[b]
+ * are written as zeros), hfinal / cfinal [B,ndir*256] (zeros for lens[b] = 0).
+ * wfrag holds W_hh [ndir,1024,256] in MFMA fragment order, [ndir][64 row tiles][16 k groups][64 lanes][4]:
+ *   wfrag[d][n][g][16 q + j][s] = W_hh[d][16 n + j][16 g + 4 q + s]
+ * One workgroup per (tile of 16 sequences, direction); no workgroup waits on another. */
+int unast_lstm_seq_fwd(const float* xproj, const float* wfrag, const float* b_ih, const float* b_hh, const int* lens, float* y,
+                       float* hfinal, float* cfinal, int B, int T, int ndir, int hidden, hipStream_t stream);
+/* One step of the decoder's additive attention for B sequences, one workgroup per sequence.
+ * mode 0, LuongGeneralAttention.forward (src/module.py:476-497): e[t] = v . tanh(Wq h[b] + mem[b,t]);
+ * mode 1, LocationSensitiveAttention.forward (src/module.py:421-463): e[t] = v . tanh(Wq h[b] + dense_w . conv(prev, cum)[t] + mem[b,t]) with
+ *         conv = Conv1d(2 -> 32, k = 31, pad 15, no bias) over [prev[b]; cum[b]] (conv_w [32,2,31], dense_w [A,32]; src/module.py:377-393).
+ * weights = softmax of e over the first lens[b] of the Tk keys (the others are exactly 0; the reference's masked_fill(-inf)),
+ * ctx[b] = weights . enc[b] ([Tk,512]).  h [B,256] (row stride ldh) is the query, Wq [A,256] the query-side projection, mem [B,Tk,A] the
+ * memory-side projection of enc (computed once per generation), v [A] the score vector; A % 4 == 0, A <= 64, Tk <= 2048.
+ * prev [B,Tk] receives the weights (mode 0: may be NULL); mode 1 reads prev and cum first and adds the weights to cum. */
+int unast_rnn_attn_step(int mode, const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc,
+                        const int* lens, float* prev, float* cum, const float* conv_w, const float* dense_w, float* ctx, int ldc,
+                        int B, int Tk, int A, hipStream_t stream);
+/* The cell update of one nn.LSTM step (src/module.py:371 at sequence length 1): gates [B,1024] = summed pre-activations (i,f,g,o),
+ * c [B,256] updated in place, h [B,256] written. */
+int unast_lstm_cell(const float* gates, int ldg, float* c, int ldc, float* h, int ldh, int B, int hidden, hipStream_t stream);
+/* x = tanh(x) over [rows, cols]: the tanh behind RNNDecoder's linear_projection (src/module.py:373). */
+int unast_tanh_rows(float* x, int ldx, int rows, int cols, hipStream_t stream);
+/* TextRNN.decode's prenet input (src/network.py:573 runs TextPrenet over the whole prefix and keeps its last position, which depends on the
+ * prefix's last 7 tokens): out [B,W,E] = embedding rows of prefix positions p-W+1 .. p, zero rows for positions before the prefix.  The prefix at
+ * device position *pos is tokens[b, 0..*pos] (generation, src/network.py:590-600; p = *pos) or, teacher_forced, [sos] at *pos = 0 and
+ * tokens[b, 0..*pos-1] after that (src/network.py:546-557; p = max(*pos,1)-1; tokens = the target).  Token ids must lie inside the table;
+ * the caller's ld_tok must cover p.  unast_window_mask clears the rows of a conv stage's output x [B,W,C] that stand for positions before the
+ * prefix (they are the next conv's zero padding).  unast_pos_advance: *pos += 1 (and *epoch += 1 if given) where no decode_end_* kernel does it. */
+int unast_text_window(const int64_t* tokens, int ld_tok, const float* emb, int E, int vocab, float* out, int B, int W, const int64_t* pos,
+                      int teacher_forced, int sos, hipStream_t stream);
+int unast_window_mask(float* x, int B, int W, int C, const int64_t* pos, int teacher_forced, hipStream_t stream);
+int unast_pos_advance(int64_t* pos, int* epoch, hipStream_t stream);
+/* The few-row contractions of one RNN decoder step (gates, projection, heads, prenet; src/module.py:362-374, src/network.py:379-392, 562-575) with
+ * plain fp32 products: Y[M,N] = act(X[M,K] . W[N,K]^T + bias + R), act 1 = ReLU, K % 4 == 0, K <= 1024.  unast_decode_linear forms its products
+ * from split-bf16 operands; greedy RNN trajectories are held to the reference's own fp32 error, so this path keeps fp32 FMAs.  X rows start at
+ * X + *pos * x_pos_stride and Y rows at Y + *pos * y_pos_stride (strides 0: plain; the frame at the position, the logits row of the position). */
+int unast_rnn_linear(const float* X, int ldx, int64_t x_pos_stride, const float* W, int ldw, const float* bias, const float* R, int ldr,
+                     float* Y, int ldy, int64_t y_pos_stride, const int64_t* pos, int M, int N, int K, int act, hipStream_t stream);
 /* LeakyReLU(slope)+Dropout of LSTMDiscriminator / Discriminator (src/network.py:160-170, 179-186); dy != NULL => backward. */
 int unast_leaky_dropout(const float* x, const float* dy, float* out, int rows, int D, float slope, float drop_p, unsigned int seed,
                         unsigned int stream_id, hipStream_t stream);

@@ -148,3 +148,64 @@ class RNNEncoder(nn.Module):
             self.reduce_h_W = nn.Linear(hidden * 2, hidden, bias=True)
             self.reduce_c_W = nn.Linear(hidden * 2, hidden, bias=True)
     forward = _no_forward
+
+
+class LuongGeneralAttention(nn.Module):
+    """src/module.py:467-497 (no biases anywhere)."""
+
+    def __init__(self, hidden_size, enc_out_size, attention_dim):
+        super().__init__()
+        self.project_hid = nn.Linear(hidden_size, attention_dim, bias=False)
+        self.project_eo = nn.Linear(enc_out_size, attention_dim, bias=False)
+        self.fc2 = nn.Linear(attention_dim, 1, bias=False)
+    forward = _no_forward
+
+
+class _LocationConv(nn.Module):
+    """src/module.py:42-73 as LocationLayer builds it: Conv1d(2 -> n_filters, k, pad (k-1)/2, no bias)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        self.conv = nn.Conv1d(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2, bias=False)
+        nn.init.xavier_uniform_(self.conv.weight, gain=nn.init.calculate_gain('linear'))
+    forward = _no_forward
+
+
+class LocationLayer(nn.Module):
+    """src/module.py:377-393."""
+
+    def __init__(self, attention_n_filters, attention_kernel_size, attention_dim):
+        super().__init__()
+        self.location_conv = _LocationConv(2, attention_n_filters, attention_kernel_size)
+        self.location_dense = Linear(attention_n_filters, attention_dim, bias=False, w_init='tanh')
+    forward = _no_forward
+
+
+class LocationSensitiveAttention(nn.Module):
+    """src/module.py:395-463."""
+
+    def __init__(self, hidden_dim, encoder_dim, attention_dim, attention_location_n_filters=32, attention_location_kernel_size=31):
+        super().__init__()
+        self.query_layer = Linear(hidden_dim, attention_dim, bias=False, w_init='tanh')
+        self.memory_layer = Linear(encoder_dim, attention_dim, bias=False, w_init='tanh')
+        self.v = Linear(attention_dim, 1, bias=False)
+        self.location_layer = LocationLayer(attention_location_n_filters, attention_location_kernel_size, attention_dim)
+    forward = _no_forward
+
+
+class RNNDecoder(nn.Module):
+    """src/module.py:340-374 with attention (the HIP decoder step is built for 'luong' and 'lsa')."""
+
+    def __init__(self, d_in, enc_out_size, hidden, dropout=.2, num_layers=1, attention=None, attn_dim=0):
+        super().__init__()
+        if attention not in ("luong", "lsa"):
+            raise NotImplementedError("the HIP RNN decoder is built with attention 'luong' or 'lsa' (got %r)" % (attention,))
+        self.attention, self.num_layers, self.p = attention, num_layers, dropout
+        self.input_size = enc_out_size + d_in
+        self.rnn = nn.LSTM(self.input_size, hidden, num_layers=num_layers, batch_first=True, dropout=dropout if num_layers > 1 else 0.0)
+        if attention == "lsa":
+            self.attention_layer = LocationSensitiveAttention(hidden, enc_out_size, attn_dim)
+        else:
+            self.attention_layer = LuongGeneralAttention(hidden, enc_out_size, attn_dim)
+        self.linear_projection = Linear(enc_out_size + hidden, hidden, w_init='tanh')
+    forward = _no_forward

@@ -4,6 +4,8 @@ by hand-written HIP kernels.
 Public surface kept:
   UNAST(text_m, speech_m, discriminator=None, teacher=None): text_ae, speech_ae, tts, asr, num_params
   TextTransformer / SpeechTransformer(args): encode, decode_sequence, forward, preprocess
+  TextRNN / SpeechRNN(args): encode, decode, decode_sequence, infer_sequence, postprocess, forward -- eval mode under torch.no_grad() at the
+      full-size RNN configuration only (unast_amd.rnn; src/network.py:279-402, 503-624); training is not built
   LSTMDiscriminator(d_in, hidden, out=1, bidirectional=False, num_layers=1, dropout=.2, relu=.2).forward(out, out_len)
   Discriminator(enc_dim, hidden=1024, out_classes=1, dropout=.2, relu=.2).forward(enc_output)
   Vocoder(num_mels, hidden_size, num_fft).forward(mel) -- eval mode under torch.no_grad() only (unast_amd.vocoder) -- and make_mags;
@@ -21,7 +23,7 @@ from . import functional as F
 from . import ops
 from .engine import Var, acc, run_segment, FlatStore, on_stream, ddp_hook
 from .module import (SpeechPrenet, SpeechPostnet, TextPrenet, TextPostnet, PositionalEncoding, TransformerEncoder,
-                     TransformerDecoder, RNNEncoder)
+                     TransformerDecoder, RNNEncoder, RNNDecoder)
 from .spec import state_dict_spec  # noqa: F401  (re-export)
 from .utils import PAD_IDX, SOS_IDX, EOS_IDX, lens_i32, next_seed  # noqa: F401
 from .vocoder import Vocoder, make_mags  # noqa: F401  (src/network.py:627-655, src/inf_vocoder.py:56-64; eval forward only)
@@ -424,6 +426,235 @@ class SpeechTransformer(AutoEncoderNet):
         from .inference import speech_generation
         return speech_generation(self, self._ctx(), memory.detach(), masks[1], max_len,
                                  lambda cx, fr, pos: F.speech_prenet_step(cx, self, fr, pos), lambda cx, mel: F.speech_postnet_residual(cx, self, mel))
+
+
+_RNN_BUILT = ("the RNN family is built for eval mode under torch.no_grad() at hidden = e_in = t_emb_dim = s_pre_hid = 256, num_layers = 2, "
+              "e_bi = True, d_attn 'luong' or 'lsa', attn_dim a multiple of 4 up to 64, num_mels a multiple of 4, teacher_ratio = 1, noise_in = False")
+
+
+def _rnn_check_args(args):
+    bad = [k for k in ("hidden", "e_in", "t_emb_dim", "s_pre_hid") if getattr(args, k) != 256]
+    if bad or args.num_layers != 2 or not args.e_bi or args.d_attn not in ("luong", "lsa") or args.attn_dim % 4 or not 4 <= args.attn_dim <= 64 \
+            or args.num_mels % 4 or args.num_mels <= 0:
+        raise NotImplementedError("%s (got hidden=%r e_in=%r t_emb_dim=%r s_pre_hid=%r num_layers=%r e_bi=%r d_attn=%r attn_dim=%r num_mels=%r)" % (
+            _RNN_BUILT, args.hidden, args.e_in, args.t_emb_dim, args.s_pre_hid, args.num_layers, args.e_bi, args.d_attn, args.attn_dim, args.num_mels))
+
+
+class _RNNModel(AutoEncoderNet):
+    """What TextRNN and SpeechRNN share (src/network.py:279-402, 503-624): the eval-path checks, the RNN encoder behind their front ends, and
+    the reference's data structures: encode returns ((h, c), enc_output), pad_mask with h, c [2,B,256], enc_output [B,T,512] and pad_mask
+    bool [B,T] (True = padded); the decoders take that pair and a pad mask (or int lengths) back."""
+
+    def _init_rnn(self, args):
+        _rnn_check_args(args)
+        self.encoder = RNNEncoder(args.e_in, args.hidden, dropout=args.e_drop, num_layers=args.num_layers, bidirectional=args.e_bi)
+        self.decoder = RNNDecoder(args.e_in, args.hidden * self.encoder.num_dir, args.hidden, dropout=args.d_drop, num_layers=args.num_layers,
+                                  attention=args.d_attn, attn_dim=args.attn_dim)
+
+    def _check_call(self, noise_in=False, teacher_ratio=1):
+        if self.training:
+            raise NotImplementedError("train() mode: " + _RNN_BUILT + "; call model.eval()")
+        if torch.is_grad_enabled():
+            raise NotImplementedError("a call with autograd enabled: " + _RNN_BUILT)
+        if noise_in:
+            raise NotImplementedError("noise_in=True is a training-time corruption: " + _RNN_BUILT)
+        if teacher_ratio != 1:
+            raise NotImplementedError("teacher_ratio=%r: %s" % (teacher_ratio, _RNN_BUILT))
+
+    def _pack(self, noise_in=False, teacher_ratio=1):
+        self._check_call(noise_in, teacher_ratio)
+        if next(self.parameters()).device.type != "cuda":
+            raise RuntimeError("unast_amd runs on the GPU only: move the model to a CUDA (ROCm) device first; there is no CPU path")
+        from . import rnn
+        return rnn.pack_of(self, self._side)
+
+    @staticmethod
+    def _enc_lens(x, lens):
+        """The packing lengths of RNNEncoder.forward (src/module.py:315-317).  pad_packed_sequence there has no total_length, so enc_output is
+        [B, max(lens), 2H] against a [B, T] pad mask: the reference only works when max(lens) == T."""
+        T = x.shape[1]
+        lens_l = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+        if len(lens_l) != x.shape[0] or min(lens_l) < 1 or max(lens_l) != T:
+            raise ValueError("encode: lengths must lie in 1..T with max(lens) == T == %d, one per sequence (got %r)" % (T, lens_l))
+        return torch.tensor(lens_l, dtype=torch.int32, device=x.device)
+
+    def _encode(self, P, x, lens_i32, pad_mask):
+        from . import rnn
+        enc_output, h, c = rnn.encoder(P, x, lens_i32)
+        return ((h, c), enc_output), pad_mask
+
+    def _lsa_state(self, B, Tk, device):
+        """The attention state a stand-alone decode() call continues from (LocationSensitiveAttention.init_memory, src/module.py:409-414)."""
+        if self.decoder.attention != "lsa":
+            return None
+        st = self.__dict__.get("_lsa_memory")
+        if st is None or st[0].shape != (B, Tk) or st[0].device != device:
+            st = (torch.zeros(B, Tk, dtype=torch.float32, device=device), torch.zeros(B, Tk, dtype=torch.float32, device=device))
+            self.__dict__["_lsa_memory"] = st
+        return st
+
+    def clear_memory(self):
+        """LocationSensitiveAttention.clear_memory (src/module.py:416-419): drops the state of stand-alone decode() calls, so that the next one
+        starts from zero weights.  decode_sequence and infer_sequence call it as the reference's do (src/network.py:340, 374, 559, 613); a
+        caller that steps decode() itself calls it between sequences."""
+        self.__dict__.pop("_lsa_memory", None)
+
+
+class TextRNN(_RNNModel):
+    """src/network.py:503-624, eval path."""
+    _prefix, _side = "text_m.", "text"
+    infer_max_len = 300
+
+    def __init__(self, args):
+        super().__init__()
+        self.prenet = TextPrenet(args.t_emb_dim, args.e_in, p=args.t_pre_drop)
+        self._init_rnn(args)
+        self.postnet = TextPostnet(args.hidden, args.t_post_drop)
+
+    def _ids(self, text, P=None):
+        """`P` given: the ids feed the decoder's window kernel, which indexes the embedding table with them unchecked, so they are checked
+        here (one read-back per call; generated ids are in range by construction)."""
+        if text.dtype != torch.int64 or text.dim() != 2 or not text.is_cuda:
+            raise ValueError("text must be an int64 CUDA tensor [B,T]")
+        if P is not None and text.numel():
+            lo, hi = (int(v) for v in torch.aminmax(text))
+            if lo < 0 or hi >= P.emb.shape[0]:
+                raise ValueError("token ids must lie in 0..%d (got %d..%d)" % (P.emb.shape[0] - 1, lo, hi))
+        return text.contiguous()
+
+    def preprocess(self, text, text_lens, noise_in=False):
+        from . import rnn
+        P = self._pack(noise_in)
+        text = self._ids(text)
+        return rnn.text_frontend(P, text), text.eq(PAD_IDX)
+
+    def encode(self, text, text_lens, noise_in=False):
+        from . import rnn
+        self._check_call(noise_in)
+        lens = self._enc_lens(text, text_lens)
+        P = self._pack()
+        text = self._ids(text)
+        return self._encode(P, rnn.text_frontend(P, text), lens, text.eq(PAD_IDX))          # the mask is text.eq(PAD_IDX), not the lengths (src/network.py:518)
+
+    def decode_sequence(self, target, tgt_lens, enc_outputs, enc_ctxt_mask, teacher_ratio=1):
+        from . import rnn
+        P = self._pack(teacher_ratio=teacher_ratio)
+        Tk = enc_outputs[1].shape[1]
+        lens_k = _lens_of_pad_mask(enc_ctxt_mask, Tk, target.device)
+        self.clear_memory()
+        return rnn.text_generation(P, enc_outputs, lens_k, target.shape[1], target=self._ids(target, P)).run()
+
+    def decode(self, input_, hidden_state, enc_output, enc_ctxt_mask):
+        """One step on a given prefix [B,L] (src/network.py:562-575): (logits [B,1,V], (h, c))."""
+        from . import rnn
+        P = self._pack()
+        B, Tk = enc_output.shape[:2]
+        lens_k = _lens_of_pad_mask(enc_ctxt_mask, Tk, input_.device)
+        g = rnn.text_generation(P, (hidden_state, enc_output), lens_k, 1, tokens=self._ids(input_, P), pos0=input_.shape[1] - 1,
+                                lsa_state=self._lsa_state(B, Tk, enc_output.device))
+        g.step(None)
+        return g.logits[:, None, :g.V].clone(), (g.core.h, g.core.c)
+
+    def postprocess(self, dec_output, distrib=False):
+        from . import rnn
+        P = self._pack()
+        shp = dec_output.shape
+        y = rnn._linear_rows(dec_output.detach().reshape(-1, shp[-1]).contiguous(), P.head_rows, P.head[1]).view(*shp[:-1], -1)
+        return torch.log_softmax(y, dim=-1) if distrib else y
+
+    def infer_sequence(self, enc_outputs, enc_ctxt_mask, max_len=300):
+        return self.generation(enc_outputs, enc_ctxt_mask, max_len).run()
+
+    def generation(self, enc_outputs, enc_ctxt_mask, max_len=None):
+        from . import rnn
+        P = self._pack()
+        Tk = enc_outputs[1].shape[1]
+        self.clear_memory()
+        return rnn.text_generation(P, enc_outputs, _lens_of_pad_mask(enc_ctxt_mask, Tk, enc_outputs[1].device), max_len or self.infer_max_len)
+
+    def forward(self, text, text_len, noise_in=False, teacher_ratio=1, ret_enc_hid=False):
+        encoder_outputs, pad_mask = self.encode(text, text_len, noise_in=noise_in)
+        pred = self.decode_sequence(text, text_len, encoder_outputs, pad_mask, teacher_ratio=1)    # 1 whatever the caller gives (src/network.py:621)
+        if ret_enc_hid:
+            return pred, encoder_outputs
+        return pred
+
+
+class SpeechRNN(_RNNModel):
+    """src/network.py:279-402, eval path."""
+    _prefix, _side = "speech_m.", "speech"
+    infer_max_len = 815
+
+    def __init__(self, args):
+        super().__init__()
+        self.prenet = SpeechPrenet(args.num_mels, args.s_pre_hid, args.e_in, p=args.s_pre_drop)
+        self._init_rnn(args)
+        self.postnet = SpeechPostnet(args.num_mels, args.hidden, p=args.s_post_drop)
+
+    def _mel(self, mel):
+        if mel.dim() != 3 or mel.shape[2] != self.postnet.num_mels or not mel.is_cuda:
+            raise ValueError("mel must be a CUDA tensor [B,T,%d]" % self.postnet.num_mels)
+        return mel.detach().to(torch.float32).contiguous()
+
+    def preprocess(self, mel, mel_lens):
+        from . import rnn
+        P = self._pack()
+        mel = self._mel(mel)
+        lens = lens_i32(mel_lens, mel.device)
+        return rnn.speech_frontend(P, mel), torch.arange(mel.shape[1], device=mel.device)[None, :] >= lens[:, None]
+
+    def encode(self, mel, mel_lens, noise_in=False):
+        from . import rnn
+        self._check_call(noise_in)
+        lens = self._enc_lens(mel, mel_lens)
+        P = self._pack()
+        mel = self._mel(mel)
+        pad_mask = torch.arange(mel.shape[1], device=mel.device)[None, :] >= lens[:, None]       # from the lengths (src/network.py:292)
+        return self._encode(P, rnn.speech_frontend(P, mel), lens, pad_mask)
+
+    def decode_sequence(self, target, target_len, enc_outputs, enc_ctxt_mask, teacher_ratio=1):
+        """Teacher-forced (src/network.py:352-377): no masking by length, target_len is handed back as the lengths."""
+        from . import rnn
+        P = self._pack(teacher_ratio=teacher_ratio)
+        Tk = enc_outputs[1].shape[1]
+        lens_k = _lens_of_pad_mask(enc_ctxt_mask, Tk, target.device)
+        self.clear_memory()
+        pre, post, stop = rnn.speech_generation(P, enc_outputs, lens_k, target.shape[1], target=self._mel(target)).run()
+        return pre, post, stop, target_len
+
+    def decode(self, input_, hidden_state, enc_output, enc_ctxt_mask):
+        """One step on a given frame [B,1,M] (src/network.py:379-392): ((mel [B,1,M], stop [B,1,1]), (h, c))."""
+        from . import rnn
+        P = self._pack()
+        B, Tk = enc_output.shape[:2]
+        lens_k = _lens_of_pad_mask(enc_ctxt_mask, Tk, input_.device)
+        g = rnn.speech_generation(P, (hidden_state, enc_output), lens_k, 1, frame=self._mel(input_), lsa_state=self._lsa_state(B, Tk, enc_output.device))
+        g.step(None)
+        return (g.head[:, None, :g.M].clone(), g.head[:, None, g.M:g.M + 1].clone()), (g.core.h, g.core.c)
+
+    def postprocess(self, dec_output, distrib=False):
+        """SpeechPostnet on [B,T,M] frames: the residual term, callers add it to their frames (src/network.py:394-395)."""
+        from . import rnn
+        P = self._pack()
+        x = self._mel(dec_output)
+        return rnn.speech_postnet_sum(P, x) - x
+
+    def infer_sequence(self, enc_outputs, enc_ctxt_mask, max_len=815):
+        return self.generation(enc_outputs, enc_ctxt_mask, max_len).run()
+
+    def generation(self, enc_outputs, enc_ctxt_mask, max_len=None):
+        from . import rnn
+        P = self._pack()
+        Tk = enc_outputs[1].shape[1]
+        self.clear_memory()
+        return rnn.speech_generation(P, enc_outputs, _lens_of_pad_mask(enc_ctxt_mask, Tk, enc_outputs[1].device), max_len or self.infer_max_len)
+
+    def forward(self, mel, mel_len, noise_in=False, ret_enc_hid=False, teacher_ratio=1):
+        encoder_outputs, pad_mask = self.encode(mel, mel_len, noise_in=noise_in)
+        pre_pred, post_pred, stop_pred, _ = self.decode_sequence(mel, mel_len, encoder_outputs, pad_mask, teacher_ratio=1)
+        if ret_enc_hid:
+            return pre_pred, post_pred, stop_pred, encoder_outputs
+        return pre_pred, post_pred, stop_pred
 
 
 class LSTMDiscriminator(_Side):

@@ -779,6 +779,171 @@ def lstm_bwd(dy, dhfinal, whh, gates, cs, lens_i32, dgates, ndir, whh_dir_stride
                                _stream()), "unast_lstm_bwd")
 
 
+# ---- RNN model family, eval path (csrc/rnn.hip) ------------------------------------------------------------
+def _dense_f32(t, name, shape=None):
+    _f32(t, name)
+    if not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError("%s must be contiguous%s (got shape %s, strides %s)" % (name, "" if shape is None else " with shape %s" % (tuple(shape),),
+                                                                              tuple(t.shape), t.stride()))
+
+
+def lstm_whh_fragments(whh):
+    """W_hh [ndir, 1024, 256] (or [1024, 256]) in the fragment order unast_lstm_seq_fwd streams: [ndir][64 row tiles][16 k groups][64 lanes][4]
+    with frag[d][n][g][16 q + j][s] = W_hh[d][16 n + j][16 g + 4 q + s].  A copy: callers cache it next to the weight."""
+    if whh.dim() == 2:
+        whh = whh.unsqueeze(0)
+    if whh.dim() != 3 or whh.shape[1:] != (1024, 256):
+        raise ValueError("lstm_whh_fragments: W_hh must be [ndir, 1024, 256] (hidden 256), got %s" % (tuple(whh.shape),))
+    nd = whh.shape[0]
+    return whh.detach().reshape(nd, 64, 16, 16, 4, 4).permute(0, 1, 3, 4, 2, 5).contiguous().view(nd, 64, 16, 64, 4)
+
+
+def lstm_seq_fwd(xproj, wfrag, b_ih, b_hh, lens_i32, y, hfinal, cfinal):
+    """One packed nn.LSTM layer's recurrence at hidden 256, forward only.  xproj [B,T,ndir*1024], wfrag = lstm_whh_fragments(W_hh),
+    b_ih / b_hh [ndir*1024] (or [ndir,1024]), lens int32 [B]; writes y [B,T,ndir*256] (zeros at t >= lens[b]), hfinal / cfinal [B,ndir*256]."""
+    if xproj.dim() != 3 or wfrag.dim() != 5 or tuple(wfrag.shape[1:]) != (64, 16, 64, 4):
+        raise ValueError("lstm_seq_fwd: xproj [B,T,ndir*1024] and wfrag [ndir,64,16,64,4] (ops.lstm_whh_fragments)")
+    B, T, _ = xproj.shape
+    ndir = wfrag.shape[0]
+    if ndir not in (1, 2) or B < 1 or T < 1:
+        raise ValueError("lstm_seq_fwd: ndir must be 1 or 2, B and T at least 1 (got ndir=%d, B=%d, T=%d)" % (ndir, B, T))
+    _dense_f32(xproj, "xproj", (B, T, ndir * 1024))
+    _dense_f32(wfrag, "wfrag")
+    for t, n in ((b_ih, "b_ih"), (b_hh, "b_hh")):
+        _f32(t, n)
+        if not t.is_contiguous() or t.numel() != ndir * 1024:
+            raise ValueError("lstm_seq_fwd: %s must hold ndir*1024 contiguous floats" % n)
+    _dense_f32(y, "y", (B, T, ndir * 256))
+    _dense_f32(hfinal, "hfinal", (B, ndir * 256))
+    _dense_f32(cfinal, "cfinal", (B, ndir * 256))
+    if not (lens_i32.is_cuda and lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.numel() == B):
+        raise TypeError("lstm_seq_fwd: lens must be a contiguous int32 CUDA tensor [B]")
+    check(lib().unast_lstm_seq_fwd(_p(xproj), _p(wfrag), _p(b_ih), _p(b_hh), _p(lens_i32), _p(y), _p(hfinal), _p(cfinal), B, T, ndir, 256, _stream()),
+          "unast_lstm_seq_fwd")
+    return y
+
+
+ATTN_LUONG, ATTN_LSA = 0, 1
+
+
+def rnn_attn_step(mode, h, Wq, mem, v, enc, lens_i32, ctx, prev=None, cum=None, conv_w=None, dense_w=None):
+    """One additive-attention step (mode ATTN_LUONG / ATTN_LSA) for B sequences: h [B,256] query rows (row stride free), Wq [A,256],
+    mem [B,Tk,A], v [A], enc [B,Tk,512], lens int32 [B]; writes ctx [B,512] (row stride free) and the weights into prev [B,Tk]
+    (optional in Luong mode).  LSA mode reads prev and cum [B,Tk], adds the weights to cum and needs conv_w [32,2,31], dense_w [A,32]."""
+    if mode not in (ATTN_LUONG, ATTN_LSA):
+        raise ValueError("rnn_attn_step: mode must be ATTN_LUONG (0) or ATTN_LSA (1), got %r" % (mode,))
+    if mem.dim() != 3 or enc.dim() != 3:
+        raise ValueError("rnn_attn_step: mem [B,Tk,A] and enc [B,Tk,512]")
+    B, Tk, A = mem.shape
+    if A % 4 or A > 64 or A < 4:
+        raise ValueError("rnn_attn_step: attn_dim must be a multiple of 4, at most 64 (got %d)" % A)
+    if not 1 <= Tk <= 2048:
+        raise ValueError("rnn_attn_step: 1 <= Tk <= 2048 (got %d)" % Tk)
+    _dense_f32(mem, "mem")
+    _dense_f32(enc, "enc", (B, Tk, 512))
+    _dense_f32(Wq, "Wq", (A, 256))
+    _f32(v, "v")
+    if not v.is_contiguous() or v.numel() != A:
+        raise ValueError("rnn_attn_step: v must hold A contiguous floats")
+    for t, n, cols in ((h, "h", 256), (ctx, "ctx", 512)):
+        _f32(t, n)
+        if t.dim() != 2 or tuple(t.shape) != (B, cols) or t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < cols or t.data_ptr() % 16:
+            raise ValueError("rnn_attn_step: %s must be [B,%d] with unit column stride and 16-byte aligned rows" % (n, cols))
+    if not (lens_i32.is_cuda and lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.numel() == B):
+        raise TypeError("rnn_attn_step: lens must be a contiguous int32 CUDA tensor [B]")
+    for t, n in ((prev, "prev"), (cum, "cum")):
+        if t is not None:
+            _dense_f32(t, n, (B, Tk))
+    if mode == ATTN_LSA:
+        if prev is None or cum is None or conv_w is None or dense_w is None:
+            raise ValueError("rnn_attn_step: LSA mode needs prev, cum, conv_w and dense_w")
+        _dense_f32(conv_w, "conv_w", (32, 2, 31))
+        _dense_f32(dense_w, "dense_w", (A, 32))
+    check(lib().unast_rnn_attn_step(mode, _p(h), h.stride(0), _p(Wq), _p(mem), _p(v), _p(enc), _p(lens_i32), _p(prev), _p(cum), _p(conv_w), _p(dense_w),
+                                    _p(ctx), ctx.stride(0), B, Tk, A, _stream()), "unast_rnn_attn_step")
+    return ctx
+
+
+def lstm_cell(gates, c, h):
+    """c, h = LSTM cell update from the summed gate pre-activations [B,1024] (i,f,g,o) at hidden 256; c [B,256] in place, h [B,256] written."""
+    B = gates.shape[0]
+    for t, n, cols in ((gates, "gates", 1024), (c, "c", 256), (h, "h", 256)):
+        _f32(t, n)
+        if t.dim() != 2 or tuple(t.shape) != (B, cols) or t.stride(1) != 1 or t.stride(0) < cols:
+            raise ValueError("lstm_cell: %s must be [B,%d] with unit column stride" % (n, cols))
+    check(lib().unast_lstm_cell(_p(gates), gates.stride(0), _p(c), c.stride(0), _p(h), h.stride(0), B, 256, _stream()), "unast_lstm_cell")
+    return h
+
+
+def tanh_rows(x2d):
+    """x = tanh(x) in place over a [rows, cols] view with unit column stride."""
+    _f32(x2d, "x")
+    if x2d.dim() != 2 or x2d.stride(1) != 1:
+        raise ValueError("tanh_rows: a 2-D view with unit column stride")
+    check(lib().unast_tanh_rows(_p(x2d), x2d.stride(0), x2d.shape[0], x2d.shape[1], _stream()), "unast_tanh_rows")
+    return x2d
+
+
+def text_window(tokens, emb, out, pos, teacher_forced, sos):
+    """out [B,W,E] = embedding rows of the last W positions of the prefix at device position `pos` (zero rows before the prefix starts).
+    tokens int64 [B,L] with unit column stride: the generated tokens (SOS first), or -- teacher_forced -- the target."""
+    B, W, E = out.shape
+    _dense_f32(out, "out")
+    _dense_f32(emb, "emb")
+    if not (tokens.is_cuda and tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.shape[0] == B and tokens.stride(1) == 1):
+        raise TypeError("text_window: tokens must be an int64 CUDA tensor [B,L] with unit column stride")
+    if emb.shape[1] != E or E % 4 or not (pos.is_cuda and pos.dtype == torch.int64):
+        raise ValueError("text_window: emb [V,E] with E % 4 == 0 matching out, pos an int64 CUDA scalar")
+    check(lib().unast_text_window(_p(tokens), tokens.stride(0), _p(emb), E, emb.shape[0], _p(out), B, W, _p(pos), int(bool(teacher_forced)), sos, _stream()),
+          "unast_text_window")
+    return out
+
+
+def window_mask(x3d, pos, teacher_forced):
+    """Clears the rows of x [B,W,C] that stand for positions before the prefix (see text_window)."""
+    _dense_f32(x3d, "x")
+    B, W, C = x3d.shape
+    if C % 4:
+        raise ValueError("window_mask: C % 4 == 0")
+    check(lib().unast_window_mask(_p(x3d), B, W, C, _p(pos), int(bool(teacher_forced)), _stream()), "unast_window_mask")
+    return x3d
+
+
+def pos_advance(pos, epoch=None):
+    check(lib().unast_pos_advance(_p(pos), _p(epoch), _stream()), "unast_pos_advance")
+
+
+def rnn_linear(X, W, bias, Y, R=None, act=0, pos=None, x_frames=None, y_frames=None):
+    """Y = act(X W^T + bias + R) with plain fp32 products for the few rows of one RNN decoder step (csrc/rnn.hip; K <= 1024).
+    x_frames [B,T,K] / y_frames [B,T,N]: the rows are the slice at the device-resident position `pos`."""
+    N, K = W.shape
+    if W.stride(1) != 1 or K % 4 or K > 1024:
+        raise ValueError("rnn_linear: W [N,K] with unit column stride, K % 4 == 0, K <= 1024 (got %s)" % (tuple(W.shape),))
+    if x_frames is not None:
+        if x_frames.dim() != 3 or x_frames.shape[2] != K or x_frames.stride(2) != 1 or pos is None:
+            raise ValueError("rnn_linear: x_frames [B,T,K] with unit column stride, and pos")
+        X, ldx, xps, M = x_frames, x_frames.stride(0), x_frames.stride(1), x_frames.shape[0]
+    else:
+        if X.dim() != 2 or X.shape[1] != K or X.stride(1) != 1:
+            raise ValueError("rnn_linear: X [M,%d] with unit column stride (got %s)" % (K, tuple(X.shape)))
+        ldx, xps, M = X.stride(0), 0, X.shape[0]
+    if y_frames is not None:
+        if y_frames.dim() != 3 or y_frames.shape[0] != M or y_frames.shape[2] < N or y_frames.stride(2) != 1 or pos is None:
+            raise ValueError("rnn_linear: y_frames [M,T,>=N] with unit column stride, and pos")
+        Y, ldy, yps = y_frames, y_frames.stride(0), y_frames.stride(1)
+    else:
+        if Y.dim() != 2 or Y.shape[0] != M or Y.shape[1] < N or Y.stride(1) != 1:
+            raise ValueError("rnn_linear: Y [M,>=N] with unit column stride")
+        ldy, yps = Y.stride(0), 0
+    if R is not None and (R.dim() != 2 or R.shape[0] != M or R.shape[1] < N or R.stride(1) != 1):
+        raise ValueError("rnn_linear: R [M,>=N] with unit column stride")
+    for t, n in ((X, "X"), (W, "W"), (bias, "bias"), (R, "R"), (Y, "Y")):
+        _f32(t, n)
+    check(lib().unast_rnn_linear(_p(X), ldx, xps, _p(W), W.stride(0), _p(bias), _p(R), R.stride(0) if R is not None else 0, _p(Y), ldy, yps, _p(pos),
+                                 M, N, K, act, _stream()), "unast_rnn_linear")
+    return Y
+
+
 def leaky_dropout(x, dy, out, slope, drop_p=0.0, seed=0, stream_id=0):
     rows = x.shape[0]
     D = x.numel() // rows

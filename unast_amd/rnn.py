@@ -1,0 +1,373 @@
+"""The RNN model family's eval path (TextRNN / SpeechRNN, src/network.py:279-402, 503-624; src/module.py:297-497) on HIP kernels.
+
+Built for the configuration every full-size reference config uses: hidden = e_in = t_emb_dim = s_pre_hid = 256, two layers, a bidirectional
+encoder, Luong or location-sensitive attention of width <= 64; eval mode under torch.no_grad() only (unast_amd.network refuses the rest).
+
+Encoder: per layer one GEMM for X W_ih^T of both directions and one unast_lstm_seq_fwd launch (csrc/rnn.hip).  Decoder: one step function
+for a position, state in device memory (position, LSTM states, attention state), so that it can be captured once as a HIP graph and replayed
+(unast_amd.inference._Generation, config.DECODE_GRAPH).  Teacher-forced decoding is the same step fed from the target buffer with the stop
+rule off.  What the kernels read is a derived, cached copy of the parameters (`Pack`), rebuilt when a parameter's or buffer's version counter
+moves: eval BatchNorm folded into tap-major conv weights, W_ih of both encoder directions as one matrix, W_hh in MFMA fragment order,
+[linear_project | stop_linear] as one head, and beside each GEMM / conv weight the residual the split-bf16 operand preparation drops.
+Every contraction keeps fp32-level products (greedy trajectories are held to the reference's own fp32 error): unast_rnn_linear for the few rows of a
+step, the three-launch split form (_linear_rows, _conv) around the many-row GEMMs and convs.
+"""
+import torch
+
+from . import ops
+from .inference import _Generation, _exit_step
+from .utils import SOS_IDX, EOS_IDX, PAD_IDX
+from .vocoder import _fold_bn
+
+_F32 = torch.float32
+WINDOW = 7            # prefix positions the last position of three 5-tap convs depends on (src/network.py:573)
+
+
+def _buf(*shape, dev):
+    return torch.empty(*shape, dtype=_F32, device=dev)
+
+
+def _c(t):
+    return t.detach().contiguous()
+
+
+class Pack:
+    """The operands the kernels read, derived from one model's parameters (module docstring)."""
+
+    def __init__(self, m, side):
+        with torch.no_grad():
+            enc, dec = m.encoder, m.decoder
+            self.enc = []
+            for l in range(enc.num_layers):
+                sfx = ("_l%d" % l, "_l%d_reverse" % l)
+                g = lambda n: [getattr(enc.rnn, n + s) for s in sfx]                       # noqa: E731
+                self.enc.append((_resid(torch.cat(g("weight_ih"))), ops.lstm_whh_fragments(torch.stack(g("weight_hh"))),
+                                 torch.cat(g("bias_ih")).contiguous(), torch.cat(g("bias_hh")).contiguous()))
+            self.reduce_h = (_c(enc.reduce_h_W.weight), _c(enc.reduce_h_W.bias))
+            self.reduce_c = (_c(enc.reduce_c_W.weight), _c(enc.reduce_c_W.bias))
+            self.dec = [tuple(_c(getattr(dec.rnn, n + "_l%d" % l)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(dec.num_layers)]
+            at = dec.attention_layer
+            if dec.attention == "lsa":
+                self.mode = ops.ATTN_LSA
+                self.Wq, self.Wmem, self.v = _c(at.query_layer.linear_layer.weight), _resid(at.memory_layer.linear_layer.weight), _c(at.v.linear_layer.weight).view(-1)
+                self.conv_w, self.dense_w = _c(at.location_layer.location_conv.conv.weight), _c(at.location_layer.location_dense.linear_layer.weight)
+            else:
+                self.mode = ops.ATTN_LUONG
+                self.Wq, self.Wmem, self.v = _c(at.project_hid.weight), _resid(at.project_eo.weight), _c(at.fc2.weight).view(-1)
+                self.conv_w = self.dense_w = None
+            self.proj = (_c(dec.linear_projection.linear_layer.weight), _c(dec.linear_projection.linear_layer.bias))
+            if side == "text":
+                pn = m.prenet
+                self.emb = _c(pn.embed.weight)
+                self.convs = [_fold_resid(getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+                self.head = (_c(m.postnet.fc1.weight), _c(m.postnet.fc1.bias))
+                self.head_rows = _resid(m.postnet.fc1.weight)
+            else:
+                pn, po = m.prenet.layer, m.postnet
+                self.fc1 = (_c(pn.fc1.linear_layer.weight), _c(pn.fc1.linear_layer.bias))
+                self.fc2 = (_c(pn.fc2.linear_layer.weight), _c(pn.fc2.linear_layer.bias))
+                self.fc1_rows, self.fc2_rows = _resid(pn.fc1.linear_layer.weight), _resid(pn.fc2.linear_layer.weight)
+                self.head = (torch.cat([po.linear_project.weight, po.stop_linear.weight]).contiguous(),
+                             torch.cat([po.linear_project.bias, po.stop_linear.bias]).contiguous())
+                self.post = [_fold_resid(po.conv1.conv, po.pre_batchnorm)] + [_fold_resid(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
+                self.post_out = (_resid(po.conv2.conv.weight.detach().permute(0, 2, 1)), _c(po.conv2.conv.bias))
+
+
+def _fold_resid(conv, bn):
+    w, b = _fold_bn(conv, bn)
+    return _resid(w), b
+
+
+def pack_of(m, side):
+    ver, dev = 0, None
+    for t in list(m.parameters()) + list(m.buffers()):
+        ver += t._version
+        dev = t.device
+    key = (ver, dev)
+    cached = m.__dict__.get("_rnn_pack")
+    if cached is None or cached[0] != key:
+        cached = (key, Pack(m, side))
+        m.__dict__["_rnn_pack"] = cached
+    return cached[1]
+
+
+def _resid(w):
+    """(w, what the GEMM's split-bf16 operand preparation drops of w): the weight pair of the fp32-level contractions below."""
+    w = w.detach().contiguous()
+    wr = torch.empty_like(w)
+    ops.split_parts(w, resid=wr)
+    return w, wr
+
+
+def _relu_(x):
+    ops.leaky_dropout(x, None, x, 0.0)
+    return x
+
+
+def _linear_rows(x2d, Wp, b, act=0):
+    """y = act(x W^T + b) for many rows with fp32-level products, Wp = _resid(W): the GEMM's three-term split-bf16 form drops x_lo W_lo and
+    what lies below 2^-17 of either operand; with x = hi + rest (hi exactly bf16) and W = W_hi + W_lo + wr, the three launches
+    hi W + rest W + x wr hold every product but the ones of order 2^-26 (the form unast_amd.train_vocoder uses)."""
+    W, Wr = Wp
+    M, K = x2d.shape
+    N = W.shape[0]
+    dev = x2d.device
+    x = x2d.contiguous()
+    xh, xr = torch.empty_like(x), torch.empty_like(x)
+    ops.split_parts(x, hi=xh, rest=xr)
+    t1, t2, y = _buf(M, N, dev=dev), _buf(M, N, dev=dev), _buf(M, N, dev=dev)
+    ops.gemm(ops.OP_KC, ops.OP_KC, xh, K, W, K, t1, N, M, N, K, bias=b)
+    ops.gemm(ops.OP_KC, ops.OP_KC, xr, K, W, K, t2, N, M, N, K, R=t1, ldr=N)
+    ops.gemm(ops.OP_KC, ops.OP_KC, x, K, Wr, K, y, N, M, N, K, R=t2, ldr=N)
+    return _relu_(y) if act else y
+
+
+def _conv(x3d, Wp, b, pad_left, out=None, work=None):
+    """out = conv(x, W) + b (no activation) with fp32-level products, Wp = _resid(tap-major W); see _linear_rows.  `work`: the four
+    temporaries (x's two parts [B,T,Cin], two partial sums [B,T,Cout]) of a caller that runs the same shape every step."""
+    W, Wr = Wp
+    B, T, _ = x3d.shape
+    dev = x3d.device
+    x = x3d.contiguous()
+    xh, xr, za, zb = work if work is not None else (torch.empty_like(x), torch.empty_like(x), _buf(B, T, W.shape[0], dev=dev), _buf(B, T, W.shape[0], dev=dev))
+    ops.split_parts(x, hi=xh, rest=xr)
+    out = out if out is not None else _buf(B, T, W.shape[0], dev=dev)
+    ops.conv_taps_fwd(xh, W, b, za, pad_left)
+    ops.conv_taps_fwd(xr, W, None, zb, pad_left, R=za)
+    ops.conv_taps_fwd(x, Wr, None, out, pad_left, R=zb)
+    return out
+
+
+# ---- encoders ---------------------------------------------------------------------------------------------------------------------------
+def text_frontend(P, text):
+    """TextPrenet over whole sequences (src/module.py:217-230, eval): embedding, three conv + BatchNorm + ReLU stages.  [B,T] -> [B,T,256]."""
+    B, T = text.shape
+    x = _buf(B * T, P.emb.shape[1], dev=text.device)
+    ops.embed_fwd(text, P.emb, x, T)
+    x = x.view(B, T, -1)
+    for wp, b in P.convs:
+        x = _relu_(_conv(x, wp, b, 2))
+    return x
+
+
+def speech_frontend(P, mel):
+    """SpeechPrenet (src/module.py:95-110, eval): two linear + ReLU layers per frame."""
+    B, T, M = mel.shape
+    h = _linear_rows(mel.reshape(B * T, M), P.fc1_rows, P.fc1[1], act=1)
+    return _linear_rows(h, P.fc2_rows, P.fc2[1], act=1).view(B, T, -1)
+
+
+def encoder(P, x, lens_i32):
+    """RNNEncoder.forward (src/module.py:313-336): the packed bidirectional LSTM stack, then reduce_h_W / reduce_c_W on each layer's
+    [forward | backward] final states.  x [B,T,256] -> (enc_output [B,T,512] with zero rows at t >= lens[b], h [L,B,256], c [L,B,256])."""
+    B, T, _ = x.shape
+    dev = x.device
+    x2 = x.reshape(B * T, -1)
+    L = len(P.enc)
+    h, c = _buf(L, B, 256, dev=dev), _buf(L, B, 256, dev=dev)
+    for l, (w_ih, wfrag, b_ih, b_hh) in enumerate(P.enc):
+        xproj = _linear_rows(x2, w_ih, None).view(B, T, -1)
+        y, hn, cn = _buf(B, T, 512, dev=dev), _buf(B, 512, dev=dev), _buf(B, 512, dev=dev)
+        ops.lstm_seq_fwd(xproj, wfrag, b_ih, b_hh, lens_i32, y, hn, cn)
+        ops.rnn_linear(hn, P.reduce_h[0], P.reduce_h[1], h[l])
+        ops.rnn_linear(cn, P.reduce_c[0], P.reduce_c[1], c[l])
+        x2 = y.view(B * T, 512)
+    return y, h, c
+
+
+# ---- decoders ---------------------------------------------------------------------------------------------------------------------------
+class _Core:
+    """What the text and the speech step share: attention, the two LSTM layers, the tanh projection (RNNDecoder.forward, src/module.py:362-374)."""
+
+    def __init__(self, P, enc, lens_k, h0, c0, lsa_state=None):
+        B, Tk, _ = enc.shape
+        dev = enc.device
+        self.P, self.enc, self.lens_k, self.B = P, enc, lens_k, B
+        A = P.Wmem[0].shape[0]
+        self.mem = _linear_rows(enc.view(B * Tk, -1), P.Wmem, None).view(B, Tk, A)       # memory-side projection, once per generation
+        self.h0, self.c0 = h0, c0
+        self.h, self.c = h0.clone(), c0.clone()
+        self.ctx = _buf(B, 512, dev=dev)
+        self.ga, self.gb = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev)
+        self.pa, self.out = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+        if P.mode == ops.ATTN_LSA:
+            self.prev, self.cum = lsa_state if lsa_state is not None else (torch.zeros(B, Tk, dtype=_F32, device=dev), torch.zeros(B, Tk, dtype=_F32, device=dev))
+        else:
+            self.prev = self.cum = None
+
+    def reset(self):
+        self.h.copy_(self.h0)
+        self.c.copy_(self.c0)
+        if self.prev is not None:
+            self.prev.zero_()
+            self.cum.zero_()
+
+    def step(self, pre):
+        """pre [B,256] (any row stride): the prenet output of this position.  Returns the decoder output [B,256]."""
+        P, h, c, ctx, ga, gb = self.P, self.h, self.c, self.ctx, self.ga, self.gb
+        # the query is the top layer's h from BEFORE this step's LSTM (src/module.py:365)
+        ops.rnn_attn_step(P.mode, h[1], P.Wq, self.mem, P.v, self.enc, self.lens_k, ctx, prev=self.prev, cum=self.cum, conv_w=P.conv_w, dense_w=P.dense_w)
+        w_ih, w_hh, b_ih, b_hh = P.dec[0]                                                  # LSTM input = [prenet | context] (src/module.py:367)
+        ops.rnn_linear(pre, w_ih[:, :256], b_ih, ga)
+        ops.rnn_linear(ctx, w_ih[:, 256:], None, gb, R=ga)
+        ops.rnn_linear(h[0], w_hh, b_hh, ga, R=gb)
+        ops.lstm_cell(ga, c[0], h[0])
+        w_ih, w_hh, b_ih, b_hh = P.dec[1]
+        ops.rnn_linear(h[0], w_ih, b_ih, gb)
+        ops.rnn_linear(h[1], w_hh, b_hh, ga, R=gb)
+        ops.lstm_cell(ga, c[1], h[1])
+        Wp, bp = P.proj                                                                    # tanh(linear_projection([lstm_out | context]))
+        ops.rnn_linear(h[1], Wp[:, :256], bp, self.pa)
+        ops.rnn_linear(ctx, Wp[:, 256:], None, self.out, R=self.pa)
+        ops.tanh_rows(self.out)
+        return self.out
+
+
+def _prep(enc_outputs, lens_k):
+    (h0, c0), enc = enc_outputs
+    return enc.detach().to(_F32).contiguous(), h0.detach().to(_F32).contiguous(), c0.detach().to(_F32).contiguous(), lens_k
+
+
+def window_bufs(P, B, dev):
+    """What text_prenet_last writes: the embedded window, the three conv outputs, and the convs' four temporaries (all [B,7,256], allocated
+    once per generation like the rest of the step's state)."""
+    return tuple(_buf(B, WINDOW, P.emb.shape[1], dev=dev) for _ in range(8))
+
+
+def text_prenet_last(P, tokens, pos_t, teacher_forced, bufs):
+    """TextPrenet over the prefix at device position pos, last position only: a window recompute (csrc/rnn.hip unast_text_window).  The three
+    convs run over the same 7-row window; rows that would need positions left of the window are never read by the row that is kept.
+    `bufs` = window_bufs(...); token ids index the embedding table unchecked (callers check given ids, TextRNN._ids)."""
+    x0, a1, a2, a3 = bufs[:4]
+    work = bufs[4:]
+    ops.text_window(tokens, P.emb, x0, pos_t, teacher_forced, SOS_IDX)
+    _relu_(_conv(x0, P.convs[0][0], P.convs[0][1], 2, out=a1, work=work))
+    ops.window_mask(a1, pos_t, teacher_forced)
+    _relu_(_conv(a1, P.convs[1][0], P.convs[1][1], 2, out=a2, work=work))
+    ops.window_mask(a2, pos_t, teacher_forced)
+    _relu_(_conv(a2, P.convs[2][0], P.convs[2][1], 2, out=a3, work=work))
+    return a3[:, WINDOW - 1, :]
+
+
+@torch.no_grad()
+def text_generation(P, enc_outputs, lens_k, max_len, target=None, tokens=None, pos0=0, lsa_state=None):
+    """TextRNN.infer_sequence (src/network.py:586-617; target None) or decode_sequence (src/network.py:539-560; target [B,T] int64, max_len = T)
+    as a _Generation.  `tokens` / `pos0`: a given prefix and its last index (TextRNN.decode, one step)."""
+    enc, h0, c0, lens_k = _prep(enc_outputs, lens_k)
+    B = enc.shape[0]
+    dev = enc.device
+    core = _Core(P, enc, lens_k, h0, c0, lsa_state)
+    tf = target is not None
+    V = P.head[0].shape[0]
+    ldl = (V + 3) // 4 * 4
+    if tf:
+        src = target.contiguous()
+        logits_all = torch.zeros(B, max_len, ldl, dtype=_F32, device=dev)
+    elif tokens is not None:
+        src = tokens.contiguous()
+    else:
+        src = torch.full((B, max_len + 1), PAD_IDX, dtype=torch.int64, device=dev)
+        src[:, 0] = SOS_IDX
+    logits = torch.zeros(B, ldl, dtype=_F32, device=dev)
+    stop_lens = torch.full((B,), max_len, dtype=torch.int64, device=dev)
+    pos_t = torch.full((1,), pos0, dtype=torch.int64, device=dev)
+    bufs = window_bufs(P, B, dev)
+
+    def reset():
+        pos_t.fill_(pos0)
+        stop_lens.fill_(max_len)
+        core.reset()
+
+    def step(epoch):
+        out = core.step(text_prenet_last(P, src, pos_t, tf, bufs))
+        if tf:
+            ops.rnn_linear(out, P.head[0], P.head[1], None, pos=pos_t, y_frames=logits_all)              # logits -> logits_all[:, pos]
+            ops.pos_advance(pos_t, epoch)
+        else:
+            ops.rnn_linear(out, P.head[0], P.head[1], logits)
+            if tokens is None:
+                ops.decode_end_text(logits, V, src, stop_lens, max_len, EOS_IDX, pos_t, epoch)             # argmax -> tokens[:, pos+1]; stop rule; pos += 1
+
+    def finish(steps):
+        if tf:
+            return logits_all[:, :, :V]
+        T = min(_exit_step(stop_lens, max_len), steps)
+        res = src[:, 1:T + 1].contiguous()
+        keep = torch.arange(T, device=dev)[None, :] < stop_lens[:, None]
+        return res * keep, stop_lens
+
+    g = _Generation(step, reset, finish, pos_t, stop_lens, max_len)
+    g.core, g.logits, g.V = core, logits, V
+    return g
+
+
+def speech_postnet_sum(P, outs):
+    """outputs + SpeechPostnet(outputs) (src/module.py:155-168, eval; src/network.py:344, 376): five causal 5-tap convs, BatchNorm folded, tanh."""
+    B, T, M = outs.shape
+    dev = outs.device
+    x = outs
+    for wp, b in P.post:
+        x = _conv(x, wp, b, 4)
+        ops.tanh_rows(x.view(B * T, -1))
+    y = _conv(x, P.post_out[0], P.post_out[1], 4)
+    ops.add_inplace(y, outs.contiguous())
+    return y
+
+
+@torch.no_grad()
+def speech_generation(P, enc_outputs, lens_k, max_len, target=None, frame=None, lsa_state=None):
+    """SpeechRNN.infer_sequence (src/network.py:312-349; target None) or decode_sequence (src/network.py:352-377; target [B,T,M], max_len = T)
+    as a _Generation.  `frame` [B,1,M]: a given input frame (SpeechRNN.decode, one step)."""
+    enc, h0, c0, lens_k = _prep(enc_outputs, lens_k)
+    B = enc.shape[0]
+    dev = enc.device
+    core = _Core(P, enc, lens_k, h0, c0, lsa_state)
+    tf = target is not None
+    M = P.head[0].shape[0] - 1
+    ldh = (M + 1 + 3) // 4 * 4
+    outputs = torch.zeros(B, max_len + 1, M, dtype=_F32, device=dev)                       # position 0 = the all-zero go frame
+    stops = torch.zeros(B, max_len + 1, dtype=_F32, device=dev)
+    if tf:
+        feed = torch.zeros(B, max_len + 1, M, dtype=_F32, device=dev)                      # step i reads target[:, i-1]; step 0 the zero frame
+        feed[:, 1:].copy_(target)
+    elif frame is not None:
+        feed = frame.detach().to(_F32).contiguous()
+    else:
+        feed = outputs
+    stop_lens = torch.full((B,), max_len, dtype=torch.int64, device=dev)                   # never moves when teacher-forced: the stop rule is off
+    rule_lens = torch.full((B,), max_len, dtype=torch.int64, device=dev) if tf else stop_lens
+    pos_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    head = torch.zeros(B, ldh, dtype=_F32, device=dev)
+    p1, pre = _buf(B, P.fc1[0].shape[0], dev=dev), _buf(B, 256, dev=dev)
+
+    def reset():
+        pos_t.zero_()
+        stop_lens.fill_(max_len)
+        rule_lens.fill_(max_len)
+        core.reset()
+
+    def step(epoch):
+        ops.rnn_linear(None, P.fc1[0], P.fc1[1], p1, act=1, pos=pos_t, x_frames=feed)                       # SpeechPrenet on the frame at pos
+        ops.rnn_linear(p1, P.fc2[0], P.fc2[1], pre, act=1)
+        out = core.step(pre)
+        ops.rnn_linear(out, P.head[0], P.head[1], head)
+        if frame is None:
+            ops.decode_end_speech(head, M, outputs, stops, rule_lens, max_len, pos_t, epoch)              # frame / stop -> pos+1; stop rule; pos += 1
+
+    def finish(steps):
+        if tf:
+            post = speech_postnet_sum(P, outputs)
+            return outputs[:, 1:], post[:, 1:], stops[:, 1:]
+        T = min(_exit_step(stop_lens, max_len), steps)
+        outs = outputs[:, :T + 1].contiguous()
+        post = speech_postnet_sum(P, outs)
+        pre_res, res = outs[:, 1:].contiguous(), post[:, 1:].contiguous()
+        res_stop = stops[:, 1:T + 1].contiguous().unsqueeze(-1)
+        ops.mask_by_len(pre_res, stop_lens)
+        ops.mask_by_len(res, stop_lens)
+        ops.mask_by_len(res_stop, stop_lens)
+        return pre_res, res, res_stop.squeeze(-1), stop_lens
+
+    g = _Generation(step, reset, finish, pos_t, stop_lens, max_len)
+    g.core, g.head, g.M = core, head, M
+    return g

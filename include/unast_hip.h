@@ -282,6 +282,25 @@ int unast_lstm_bwd(const float* dy, const float* dhfinal, const float* whh, cons
  * One workgroup per (tile of 16 sequences, direction); no workgroup waits on another. */
 int unast_lstm_seq_fwd(const float* xproj, const float* wfrag, const float* b_ih, const float* b_hh, const int* lens, float* y,
                        float* hfinal, float* cfinal, int B, int T, int ndir, int hidden, hipStream_t stream);
+/* unast_lstm_seq_fwd_train: unast_lstm_seq_fwd (the same arithmetic in the same order: y, hfinal and cfinal are bit-identical) that also
+ * stores what the backward of src/module.py:306, 315-317 reads:
+ *   saved [B,T,ndir,5,256]  the activations i, f, g, o and the cell state c_t of every live (b, t, dir, unit); rows t >= lens[b] are neither
+ *                           written nor read (the caller need not clear them);
+ *   hprev [B,T,ndir*256]    h_{t-1} in the direction's own order (zero at a sequence's first step in its direction); rows t >= lens[b] are
+ *                           written as zeros, so dW_hh[d] = dxproj[:, :, d]^T . hprev[:, :, d] is a plain GEMM over all B T rows.
+ * unast_lstm_seq_bwd: backpropagation through time of that recurrence.  dy [B,T,ndir*256] (rows t >= lens[b] are never read),
+ * dhfinal / dcfinal [B,ndir*256] (either may be NULL = zero) enter at the sequence's own last forward step (t = lens[b]-1 forward, t = 0
+ * reverse).  dxproj [B,T,ndir*1024] receives the gradient of the gate pre-activations = of the forward's xproj input (rows t >= lens[b]
+ * are written as exact zeros); dW_ih, dx and both bias gradients are GEMMs and column sums over it.
+ * wfrag_t holds W_hh [ndir,1024,256] as the B operand [k = gate row][n = unit], [ndir][16 unit tiles][64 k groups][64 lanes][4]:
+ *   wfrag_t[d][n][g][16 q + j][s] = W_hh[d][16 g + 4 q + s][16 n + j]
+ * One 512-thread workgroup per (tile of 16 sequences, direction); no workgroup waits on another, no atomics: results are reproducible to
+ * the bit.  Hidden 256 only. */
+int unast_lstm_seq_fwd_train(const float* xproj, const float* wfrag, const float* b_ih, const float* b_hh, const int* lens, float* y,
+                             float* hfinal, float* cfinal, float* saved, float* hprev, int B, int T, int ndir, int hidden,
+                             hipStream_t stream);
+int unast_lstm_seq_bwd(const float* dy, const float* dhfinal, const float* dcfinal, const float* wfrag_t, const float* saved,
+                       const int* lens, float* dxproj, int B, int T, int ndir, int hidden, hipStream_t stream);
 /* One step of the decoder's additive attention for B sequences, one workgroup per sequence.
  * mode 0, LuongGeneralAttention.forward (src/module.py:476-497): e[t] = v . tanh(Wq h[b] + mem[b,t]);
  * mode 1, LocationSensitiveAttention.forward (src/module.py:421-463): e[t] = v . tanh(Wq h[b] + dense_w . conv(prev, cum)[t] + mem[b,t]) with

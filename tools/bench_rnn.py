@@ -2,7 +2,9 @@
 """Times the RNN model family's eval path on the GPU (HIP events, warm-up, medians): unast_lstm_seq_fwd per recurrent step, both encoders,
 one decoded position eager and replayed for both models and both attention types, and a whole tts(infer) cut to --frames frames (the text
 encoder plus SpeechRNN.infer_sequence(max_len=frames); UNAST.tts itself always decodes up to infer_sequence's default of 815).
-Sizes: B = 32, T_text = 180, T_mel = 800.  Usage: python tools/bench_rnn.py [--reps 7] [--frames 800]"""
+Sizes: B = 32, T_text = 180, T_mel = 800.  --train: the encoder-training mode instead -- unast_lstm_seq_fwd_train next to unast_lstm_seq_fwd,
+unast_lstm_seq_bwd per recurrent step, and train_rnn.encoder_forward + encoder_backward of both models (dropout and noise on).
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train]"""
 import argparse
 import os
 import statistics
@@ -20,6 +22,7 @@ from unast_amd.portable import synth_batch  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--frames", type=int, default=800)
+ap.add_argument("--train", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -47,6 +50,45 @@ def models(attn):
         m.load_state_dict(rnn_weights.state_dict(side, list(sd), [list(v.shape) for v in sd.values()], 1234))
     return tm.to(D).eval(), sm.to(D).eval()
 
+
+def train_mode():
+    from unast_amd import train_rnn
+    g = torch.Generator().manual_seed(0)
+    for T in (TM, TT):
+        xproj = torch.randn(B, T, 2048, generator=g).to(D)
+        whh = (torch.randn(2, 1024, 256, generator=g) / 16).to(D)
+        wfrag, wfrag_t = ops.lstm_whh_fragments(whh), ops.lstm_whh_fragments_bwd(whh)
+        bias = torch.zeros(2048, device=D)
+        lens = torch.full((B,), T, dtype=torch.int32, device=D)
+        y, hn, cn = torch.empty(B, T, 512, device=D), torch.empty(B, 512, device=D), torch.empty(B, 512, device=D)
+        saved, hprev = torch.empty(B, T, 2, 5, 256, device=D), torch.empty(B, T, 512, device=D)
+        dy, dfin, dxproj = torch.randn(B, T, 512, generator=g).to(D), torch.randn(B, 512, generator=g).to(D), torch.empty(B, T, 2048, device=D)
+        ev = median_ms(lambda: ops.lstm_seq_fwd(xproj, wfrag, bias, bias, lens, y, hn, cn))
+        tr = median_ms(lambda: ops.lstm_seq_fwd_train(xproj, wfrag, bias, bias, lens, y, hn, cn, saved, hprev))
+        bw = median_ms(lambda: ops.lstm_seq_bwd(dy, wfrag_t, saved, lens, dxproj, dhfinal=dfin, dcfinal=dfin))
+        print("B=%d T=%d ndir=2: lstm_seq_fwd %.2f ms (%.2f us/step), lstm_seq_fwd_train %.2f ms (%.2f us/step, x %.3f), lstm_seq_bwd %.2f ms "
+              "(%.2f us/step, x %.2f of the forward)" % (B, T, ev, ev * 1e3 / T, tr, tr * 1e3 / T, tr / ev, bw, bw * 1e3 / T, bw / ev))
+    text, mel, text_len, mel_len = (torch.from_numpy(x) for x in synth_batch(B, TT, TM, seed=3))
+    text, mel = text.to(D), mel.to(D)
+    tm, sm = models("luong")
+    tm.train(), sm.train()
+    for name, m, x, ln, T in (("text", tm, text, text_len, TT), ("speech", sm, mel, mel_len, TM)):
+        ln = ln.clone()
+        ln[0] = T                                                      # encode's rule: max(lens) == T
+        cot = (torch.randn(B, T, 512, device=D), torch.randn(2, B, 256, device=D), torch.randn(2, B, 256, device=D))
+        tapes = []
+        fw = median_ms(lambda: tapes.append(train_rnn.encoder_forward(m, x, ln, noise_in=True, seed=len(tapes))))
+
+        def both():
+            train_rnn.encoder_backward(train_rnn.encoder_forward(m, x, ln, noise_in=True, seed=1), *cot)
+        del tapes[:]
+        fb = median_ms(both)
+        print("%s encoder, B=%d T=%d, dropout and noise on: encoder_forward %.2f ms, encoder_forward + encoder_backward %.2f ms" % (name, B, T, fw, fb))
+
+
+if a.train:
+    train_mode()
+    sys.exit(0)
 
 with torch.no_grad():
     # the recurrence alone

@@ -1,6 +1,7 @@
-// Kernels of the RNN model family's eval path (TextRNN / SpeechRNN, src/network.py:279-402, 503-624; src/module.py:297-497) at the
-// width every full-size reference config uses: hidden 256.
-//   lstm_seq_fwd_kernel   recurrence of one packed nn.LSTM layer (src/module.py:306, 315-317), forward only
+// Kernels of the RNN model family (TextRNN / SpeechRNN, src/network.py:279-402, 503-624; src/module.py:297-497) at the width every
+// full-size reference config uses, hidden 256: the eval path and the encoders' training (unast_amd/train_rnn.py).
+//   lstm_seq_fwd_kernel   recurrence of one packed nn.LSTM layer (src/module.py:306, 315-317); <true> also saves what the backward reads
+//   lstm_seq_bwd_kernel   backpropagation through time of that recurrence
 //   rnn_attn_step_kernel  one step of Luong / location-sensitive additive attention (src/module.py:395-497)
 //   lstm_cell_kernel      pointwise cell update of one decoder step (the nn.LSTM call of src/module.py:371 at sequence length 1)
 #include "common.h"
@@ -23,10 +24,18 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // lane is the B operand of four consecutive k-steps, a wave's load is 1 KiB contiguous.
 // MFMA k order: k-step s of group g takes k = 16 g + 4 (lane >> 4) + s from both operands (any permutation of k is a valid contraction
 // as long as A and B agree), which makes the A operand a float4 of the row-major h row.
+//
+// TRAIN (unast_lstm_seq_fwd_train): the same instructions in the same order on y, hfinal and cfinal, plus what unast_lstm_seq_bwd reads:
+//   saved [B,T,ndir,5,256]   the activations i, f, g, o and the cell state c_t of every live (b, t, dir, unit); rows t >= lens[b] are neither
+//                            written here nor read by the backward
+//   hprev [B,T,ndir*256]     h_{t-1} in the direction's own order (zero at a sequence's first step in its direction); rows t >= lens[b] are
+//                            written as zeros, since dW_hh = dxproj^T hprev is a GEMM over all B T rows
+template <bool TRAIN>
 __global__ __launch_bounds__(SEQ_THREADS) void lstm_seq_fwd_kernel(const float* __restrict__ xproj, const float* __restrict__ wfrag,
                                                                    const float* __restrict__ b_ih, const float* __restrict__ b_hh,
                                                                    const int* __restrict__ lens, float* __restrict__ y, float* __restrict__ hfinal,
-                                                                   float* __restrict__ cfinal, int B, int T, int ndir) {
+                                                                   float* __restrict__ cfinal, float* __restrict__ saved, float* __restrict__ hprev,
+                                                                   int B, int T, int ndir) {
     __shared__ __attribute__((aligned(16))) float hs[2][SEQ_TILE][LDH];
     __shared__ int s_len[SEQ_TILE];
     const int dir = blockIdx.y, b0 = blockIdx.x * SEQ_TILE;
@@ -87,6 +96,10 @@ __global__ __launch_bounds__(SEQ_THREADS) void lstm_seq_fwd_kernel(const float* 
                 if (live_r[r]) {
                     float* yp = y + ((size_t)(b0 + 4 * q + r) * T + s) * yrow + (size_t)dir * RH + unit0;
                     yp[0] = 0.f; yp[16] = 0.f;
+                    if constexpr (TRAIN) {
+                        float* hp = hprev + ((size_t)(b0 + 4 * q + r) * T + s) * yrow + (size_t)dir * RH + unit0;
+                        hp[0] = 0.f; hp[16] = 0.f;
+                    }
                 }
             continue;
         }
@@ -133,10 +146,17 @@ __global__ __launch_bounds__(SEQ_THREADS) void lstm_seq_fwd_kernel(const float* 
             float* yp = y + ((size_t)(b0 + 4 * q + r) * T + t) * yrow + (size_t)dir * RH + unit0;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
+                if constexpr (TRAIN) {
+                    if (live_r[r]) hprev[((size_t)(b0 + 4 * q + r) * T + t) * yrow + (size_t)dir * RH + unit0 + 16 * u] = on ? h[u][r] : 0.f;
+                }
                 if (on) {
                     const float ig = sigmoidf_(acc[0][u][r]), fg = sigmoidf_(acc[1][u][r]), gg = tanhf(acc[2][u][r]), og = sigmoidf_(acc[3][u][r]);
                     c[u][r] = fg * c[u][r] + ig * gg;
                     h[u][r] = og * tanhf(c[u][r]);
+                    if constexpr (TRAIN) {
+                        float* sp = saved + (((size_t)(b0 + 4 * q + r) * T + t) * ndir + dir) * (5 * RH) + unit0 + 16 * u;
+                        sp[0] = ig; sp[RH] = fg; sp[2 * RH] = gg; sp[3 * RH] = og; sp[4 * RH] = c[u][r];
+                    }
                 }
                 if (live_r[r]) yp[16 * u] = on ? h[u][r] : 0.f;
                 hs[cur ^ 1][4 * q + r][unit0 + 16 * u] = h[u][r];
@@ -158,6 +178,158 @@ __global__ __launch_bounds__(SEQ_THREADS) void lstm_seq_fwd_kernel(const float* 
 #pragma unroll
             for (int u = 0; u < 2; ++u) { hfinal[o + 16 * u] = h[u][r]; cfinal[o + 16 * u] = c[u][r]; }
         }
+}
+
+// Backward of lstm_seq_fwd_kernel<true> through time for a tile of 16 sequences of one direction, in the reverse of the forward's step order.
+// Per step: dh = dy[b,t] + dh_rec (+ dhfinal / dcfinal at the sequence's own last forward step, s = len - 1: t = len - 1 forward, t = 0
+// reverse), the pointwise gate gradients from `saved` (layout: lstm_seq_fwd_kernel), dG_t [16,1024] to global memory as dxproj [B,T,ndir*1024]
+// (the gradient of the forward's xproj input) and to LDS, then dh_rec [16,256] = dG_t [16,1024] x W_hh [1024,256] on v_mfma_f32_16x16x4_f32.
+// A wave owns hidden units [32 w, 32 w + 32): two 16x16 output tiles, each summed over its 256 k-steps in two interleaved chains (four
+// independent accumulators per wave), 512 MFMAs per wave and step as in the forward.  The accumulator lane layout is the forward's gate
+// layout, so dh_rec, dc and the pointwise step stay in the lane's registers; only dG_t goes through LDS (two buffers of 16 rows of 1024 + 4
+// floats, 128.5 KiB, one barrier per step: a wave writes buffer s & 1 two barriers after the last read of it).
+// W_hh is streamed from L2 every step in a second fragment order (wfrag_t, ops.lstm_whh_fragments_bwd), the B operand [k = gate row][n = unit]:
+//   wfrag_t[d][n][g][16 q + j][s] = W_hh[d][16 g + 4 q + s][16 n + j]      n: 16 unit tiles, g: 64 k groups
+// so that the A operand of the group's four k-steps is a float4 of the LDS row.
+// A row that is not live at step s (s >= len, or tile padding) writes a zero dG row: its dh_rec stays zero until its own last step.  dy and
+// saved at t >= lens[b] are never read; dxproj at t >= lens[b] is written as exact zeros; steps past the tile's longest sequence skip the product.
+constexpr int LDG = RG + 4;          // LDS row of one sequence's dG (floats; padded by one 16-byte slot)
+
+__global__ __launch_bounds__(SEQ_THREADS) void lstm_seq_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ dhfinal,
+                                                                   const float* __restrict__ dcfinal, const float* __restrict__ wfrag_t,
+                                                                   const float* __restrict__ saved, const int* __restrict__ lens,
+                                                                   float* __restrict__ dxproj, int B, int T, int ndir) {
+    __shared__ __attribute__((aligned(16))) float gs[2][SEQ_TILE][LDG];
+    __shared__ int s_len[SEQ_TILE];
+    const int dir = blockIdx.y, b0 = blockIdx.x * SEQ_TILE;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
+
+    if (tid < SEQ_TILE) {
+        int n = 0;
+        if (b0 + tid < B) n = min(max(lens[b0 + tid], 0), T);
+        s_len[tid] = n;
+    }
+    __syncthreads();
+    int tmax = 0;
+#pragma unroll
+    for (int i = 0; i < SEQ_TILE; ++i) tmax = max(tmax, s_len[i]);
+    int len_r[4];
+    bool live_r[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { len_r[r] = s_len[4 * q + r]; live_r[r] = b0 + 4 * q + r < B; }
+
+    const float4* wf = reinterpret_cast<const float4*>(wfrag_t) + (size_t)dir * (RG * RH / 4);
+    const int unit0 = wave * 32 + j;                  // + 16 u
+    const size_t xrow = (size_t)ndir * RG, yrow = (size_t)ndir * RH;
+
+    // padding rows of dxproj past the tile's longest sequence
+    for (int s = tmax; s < T; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (live_r[r]) {
+                float* dp = dxproj + ((size_t)(b0 + 4 * q + r) * T + s) * xrow + (size_t)dir * RG + unit0;
+#pragma unroll
+                for (int G = 0; G < 4; ++G) { dp[G * RH] = 0.f; dp[G * RH + 16] = 0.f; }
+            }
+
+    // what step s reads: v[0..3] = i, f, g, o, v[4] = c_t, v[5] = c_{t-1} (the cell state of step s - 1; zero at s = 0), v[6] = dy
+    auto load_step = [&](int s, float (&v)[7][2][4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool on = s >= 0 && s < len_r[r];
+            const int t = dir ? len_r[r] - 1 - s : s;
+            const int tp = dir ? t + 1 : t - 1;
+            const size_t row = (size_t)(b0 + 4 * q + r) * T;
+            const float* sp = saved + ((row + (on ? t : 0)) * ndir + dir) * (5 * RH) + unit0;
+            const float* cp = saved + ((row + (on && s > 0 ? tp : 0)) * ndir + dir) * (5 * RH) + 4 * RH + unit0;
+            const float* yp = dy + (row + (on ? t : 0)) * yrow + (size_t)dir * RH + unit0;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) v[k][u][r] = on ? sp[k * RH + 16 * u] : 0.f;
+                v[5][u][r] = on && s > 0 ? cp[16 * u] : 0.f;
+                v[6][u][r] = on ? yp[16 * u] : 0.f;
+            }
+        }
+    };
+
+    float dhr[2][4], dc[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { dhr[u][r] = 0.f; dc[u][r] = 0.f; }
+    float vc[7][2][4], vn[7][2][4];
+    load_step(tmax - 1, vc);
+
+    for (int s = tmax - 1; s >= 0; --s) {
+        const int cur = s & 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool on = s < len_r[r];
+            const bool last = s == len_r[r] - 1;
+            const int t = on ? (dir ? len_r[r] - 1 - s : s) : s;       // a finished sequence's row s is padding
+            const size_t fo = (size_t)(b0 + 4 * q + r) * yrow + (size_t)dir * RH + unit0;
+            float* dp = dxproj + ((size_t)(b0 + 4 * q + r) * T + t) * xrow + (size_t)dir * RG + unit0;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;
+                if (on) {
+                    float dh = vc[6][u][r] + dhr[u][r];
+                    if (last) {
+                        if (dhfinal) dh += dhfinal[fo + 16 * u];
+                        if (dcfinal) dc[u][r] += dcfinal[fo + 16 * u];
+                    }
+                    const float ia = vc[0][u][r], fa = vc[1][u][r], ga = vc[2][u][r], oa = vc[3][u][r];
+                    const float tc = tanhf(vc[4][u][r]);
+                    const float dct = dc[u][r] + dh * oa * (1.f - tc * tc);
+                    go = dh * tc * oa * (1.f - oa);
+                    gi = dct * ga * ia * (1.f - ia);
+                    gg = dct * ia * (1.f - ga * ga);
+                    gf = dct * vc[5][u][r] * fa * (1.f - fa);
+                    dc[u][r] = dct * fa;
+                }
+                if (live_r[r]) { dp[16 * u] = gi; dp[RH + 16 * u] = gf; dp[2 * RH + 16 * u] = gg; dp[3 * RH + 16 * u] = go; }
+                float* lp = &gs[cur][4 * q + r][unit0 + 16 * u];
+                lp[0] = gi; lp[RH] = gf; lp[2 * RH] = gg; lp[3 * RH] = go;
+            }
+        }
+        if (s == 0) break;                            // nothing reads the first step's dh_rec
+        load_step(s - 1, vn);
+        __syncthreads();
+
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[u][h][r] = 0.f;
+#pragma unroll 4
+        for (int g = 0; g < 64; ++g) {
+            const float4 a = *reinterpret_cast<const float4*>(&gs[cur][j][g * 16 + q * 4]);
+            float4 w[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) w[u] = wf[((size_t)((wave * 2 + u) * 64 + g)) * 64 + lane];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[u].x, acc[u][0], 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[u].y, acc[u][1], 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[u].z, acc[u][0], 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[u].w, acc[u][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dhr[u][r] = acc[u][0][r] + acc[u][1][r];
+#pragma unroll
+        for (int k = 0; k < 7; ++k)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) vc[k][u][r] = vn[k][u][r];
+    }
 }
 
 // ---- additive attention, one decoder step -----------------------------------------------------------------------------------------
@@ -401,9 +573,32 @@ extern "C" int unast_lstm_seq_fwd(const float* xproj, const float* wfrag, const 
     UNAST_REQUIRE(hidden == RH, "unast_lstm_seq_fwd: built for hidden=%d only (got %d); hidden 64 / 128 are unast_lstm_fwd's", RH, hidden);
     UNAST_REQUIRE(B > 0 && T > 0 && (ndir == 1 || ndir == 2), "unast_lstm_seq_fwd: bad dims (B=%d, T=%d, ndir=%d)", B, T, ndir);
     UNAST_REQUIRE((((uintptr_t)wfrag) & 15) == 0, "unast_lstm_seq_fwd: the W_hh fragments must be 16-byte aligned");
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3((B + SEQ_TILE - 1) / SEQ_TILE, ndir), dim3(SEQ_THREADS), 0, stream, xproj, wfrag, b_ih, b_hh, lens, y,
-                       hfinal, cfinal, B, T, ndir);
+    hipLaunchKernelGGL(lstm_seq_fwd_kernel<false>, dim3((B + SEQ_TILE - 1) / SEQ_TILE, ndir), dim3(SEQ_THREADS), 0, stream, xproj, wfrag, b_ih, b_hh,
+                       lens, y, hfinal, cfinal, (float*)nullptr, (float*)nullptr, B, T, ndir);
     return unast_check_launch("unast_lstm_seq_fwd");
+}
+
+extern "C" int unast_lstm_seq_fwd_train(const float* xproj, const float* wfrag, const float* b_ih, const float* b_hh, const int* lens, float* y,
+                                        float* hfinal, float* cfinal, float* saved, float* hprev, int B, int T, int ndir, int hidden,
+                                        hipStream_t stream) {
+    UNAST_REQUIRE(xproj && wfrag && b_ih && b_hh && lens && y && hfinal && cfinal && saved && hprev, "unast_lstm_seq_fwd_train: null pointer");
+    UNAST_REQUIRE(hidden == RH, "unast_lstm_seq_fwd_train: built for hidden=%d only (got %d)", RH, hidden);
+    UNAST_REQUIRE(B > 0 && T > 0 && (ndir == 1 || ndir == 2), "unast_lstm_seq_fwd_train: bad dims (B=%d, T=%d, ndir=%d)", B, T, ndir);
+    UNAST_REQUIRE((((uintptr_t)wfrag) & 15) == 0, "unast_lstm_seq_fwd_train: the W_hh fragments must be 16-byte aligned");
+    hipLaunchKernelGGL(lstm_seq_fwd_kernel<true>, dim3((B + SEQ_TILE - 1) / SEQ_TILE, ndir), dim3(SEQ_THREADS), 0, stream, xproj, wfrag, b_ih, b_hh,
+                       lens, y, hfinal, cfinal, saved, hprev, B, T, ndir);
+    return unast_check_launch("unast_lstm_seq_fwd_train");
+}
+
+extern "C" int unast_lstm_seq_bwd(const float* dy, const float* dhfinal, const float* dcfinal, const float* wfrag_t, const float* saved,
+                                  const int* lens, float* dxproj, int B, int T, int ndir, int hidden, hipStream_t stream) {
+    UNAST_REQUIRE(dy && wfrag_t && saved && lens && dxproj, "unast_lstm_seq_bwd: null pointer");
+    UNAST_REQUIRE(hidden == RH, "unast_lstm_seq_bwd: built for hidden=%d only (got %d); hidden 64 / 128 are unast_lstm_bwd's", RH, hidden);
+    UNAST_REQUIRE(B > 0 && T > 0 && (ndir == 1 || ndir == 2), "unast_lstm_seq_bwd: bad dims (B=%d, T=%d, ndir=%d)", B, T, ndir);
+    UNAST_REQUIRE((((uintptr_t)wfrag_t) & 15) == 0, "unast_lstm_seq_bwd: the W_hh fragments must be 16-byte aligned");
+    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3((B + SEQ_TILE - 1) / SEQ_TILE, ndir), dim3(SEQ_THREADS), 0, stream, dy, dhfinal, dcfinal, wfrag_t,
+                       saved, lens, dxproj, B, T, ndir);
+    return unast_check_launch("unast_lstm_seq_bwd");
 }
 
 extern "C" int unast_rnn_attn_step(int mode, const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc,

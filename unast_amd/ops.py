@@ -779,7 +779,7 @@ def lstm_bwd(dy, dhfinal, whh, gates, cs, lens_i32, dgates, ndir, whh_dir_stride
                                _stream()), "unast_lstm_bwd")
 
 
-# ---- RNN model family, eval path (csrc/rnn.hip) ------------------------------------------------------------
+# ---- RNN model family: eval path and encoder training (csrc/rnn.hip) --------------------------------------
 def _dense_f32(t, name, shape=None):
     _f32(t, name)
     if not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
@@ -821,6 +821,64 @@ def lstm_seq_fwd(xproj, wfrag, b_ih, b_hh, lens_i32, y, hfinal, cfinal):
     check(lib().unast_lstm_seq_fwd(_p(xproj), _p(wfrag), _p(b_ih), _p(b_hh), _p(lens_i32), _p(y), _p(hfinal), _p(cfinal), B, T, ndir, 256, _stream()),
           "unast_lstm_seq_fwd")
     return y
+
+
+def lstm_whh_fragments_bwd(whh):
+    """W_hh [ndir, 1024, 256] (or [1024, 256]) in the fragment order unast_lstm_seq_bwd streams, the B operand [k = gate row][n = unit]:
+    [ndir][16 unit tiles][64 k groups][64 lanes][4] with frag[d][n][g][16 q + j][s] = W_hh[d][16 g + 4 q + s][16 n + j].  A copy."""
+    if whh.dim() == 2:
+        whh = whh.unsqueeze(0)
+    if whh.dim() != 3 or whh.shape[1:] != (1024, 256):
+        raise ValueError("lstm_whh_fragments_bwd: W_hh must be [ndir, 1024, 256] (hidden 256), got %s" % (tuple(whh.shape),))
+    nd = whh.shape[0]
+    return whh.detach().reshape(nd, 64, 4, 4, 16, 16).permute(0, 4, 1, 2, 5, 3).contiguous().view(nd, 16, 64, 64, 4)
+
+
+def _lstm_seq_dims(name, lead, lead_cols, wfrag, frag_shape, lens_i32):
+    if lead.dim() != 3 or wfrag.dim() != 5 or tuple(wfrag.shape[1:]) != frag_shape:
+        raise ValueError("%s: a [B,T,ndir*%d] operand and W_hh fragments [ndir,%d,%d,%d,%d]" % ((name, lead_cols) + frag_shape))
+    B, T, _ = lead.shape
+    ndir = wfrag.shape[0]
+    if ndir not in (1, 2) or B < 1 or T < 1:
+        raise ValueError("%s: ndir must be 1 or 2, B and T at least 1 (got ndir=%d, B=%d, T=%d)" % (name, ndir, B, T))
+    _dense_f32(lead, name + " operand", (B, T, ndir * lead_cols))
+    _dense_f32(wfrag, "wfrag")
+    if not (lens_i32.is_cuda and lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.numel() == B):
+        raise TypeError("%s: lens must be a contiguous int32 CUDA tensor [B]" % name)
+    return B, T, ndir
+
+
+def lstm_seq_fwd_train(xproj, wfrag, b_ih, b_hh, lens_i32, y, hfinal, cfinal, saved, hprev):
+    """lstm_seq_fwd (bit-identical y, hfinal, cfinal) that also writes what lstm_seq_bwd reads: saved [B,T,ndir,5,256] (i, f, g, o, c_t; rows
+    t >= lens[b] are left as they are and never read) and hprev [B,T,ndir*256] (h_{t-1}; zeros at t >= lens[b])."""
+    B, T, ndir = _lstm_seq_dims("lstm_seq_fwd_train", xproj, 1024, wfrag, (64, 16, 64, 4), lens_i32)
+    for t, n in ((b_ih, "b_ih"), (b_hh, "b_hh")):
+        _f32(t, n)
+        if not t.is_contiguous() or t.numel() != ndir * 1024:
+            raise ValueError("lstm_seq_fwd_train: %s must hold ndir*1024 contiguous floats" % n)
+    _dense_f32(y, "y", (B, T, ndir * 256))
+    _dense_f32(hfinal, "hfinal", (B, ndir * 256))
+    _dense_f32(cfinal, "cfinal", (B, ndir * 256))
+    _dense_f32(saved, "saved", (B, T, ndir, 5, 256))
+    _dense_f32(hprev, "hprev", (B, T, ndir * 256))
+    check(lib().unast_lstm_seq_fwd_train(_p(xproj), _p(wfrag), _p(b_ih), _p(b_hh), _p(lens_i32), _p(y), _p(hfinal), _p(cfinal), _p(saved), _p(hprev),
+                                         B, T, ndir, 256, _stream()), "unast_lstm_seq_fwd_train")
+    return y
+
+
+def lstm_seq_bwd(dy, wfrag_t, saved, lens_i32, dxproj, dhfinal=None, dcfinal=None):
+    """Backward of lstm_seq_fwd_train's recurrence.  dy [B,T,ndir*256] (rows t >= lens[b] are not read), wfrag_t = lstm_whh_fragments_bwd(W_hh),
+    saved as lstm_seq_fwd_train wrote it, dhfinal / dcfinal [B,ndir*256] or None (zero); writes dxproj [B,T,ndir*1024], the gradient of the
+    gate pre-activations (exact zeros at t >= lens[b])."""
+    B, T, ndir = _lstm_seq_dims("lstm_seq_bwd", dy, 256, wfrag_t, (16, 64, 64, 4), lens_i32)
+    _dense_f32(saved, "saved", (B, T, ndir, 5, 256))
+    _dense_f32(dxproj, "dxproj", (B, T, ndir * 1024))
+    for t, n in ((dhfinal, "dhfinal"), (dcfinal, "dcfinal")):
+        if t is not None:
+            _dense_f32(t, n, (B, ndir * 256))
+    check(lib().unast_lstm_seq_bwd(_p(dy), _p(dhfinal), _p(dcfinal), _p(wfrag_t), _p(saved), _p(lens_i32), _p(dxproj), B, T, ndir, 256, _stream()),
+          "unast_lstm_seq_bwd")
+    return dxproj
 
 
 ATTN_LUONG, ATTN_LSA = 0, 1

@@ -315,6 +315,40 @@ int unast_rnn_attn_step(int mode, const float* h, int ldh, const float* Wq, cons
 /* The cell update of one nn.LSTM step (src/module.py:371 at sequence length 1): gates [B,1024] = summed pre-activations (i,f,g,o),
  * c [B,256] updated in place, h [B,256] written. */
 int unast_lstm_cell(const float* gates, int ldg, float* c, int ldc, float* h, int ldh, int B, int hidden, hipStream_t stream);
+/* --- SpeechRNN decoder training (unast_amd/train_rnn.py decoder_forward / decoder_backward; src/network.py:352-377 in train mode) ---
+ * unast_rnn_attn_step_train: unast_rnn_attn_step out of place (the same kernel: ctx and the weights carry the same bits).  Mode 1 reads
+ * prev_in / cum_in [B,Tk] (row stride ld_in); the weights go to w_out and, mode 1, cum_in + weights to cum_out (row stride ld_out), so
+ * that a caller keeps the weights of every position and the cum each position read.  No output may be an input.
+ * unast_rnn_attn_step_bwd: backward of one such position.  Inputs: d_ctx [B,512], the saved weights w and (mode 1) the prev / cum the
+ * position read (row stride ldw), the query h [B,256], Wq, mem, v, enc, lens as the forward took them, and the incoming gradient of the
+ * weights d_w_a + d_w_b [B,Tk] (row stride ldd; either may be NULL = zero): location-sensitive attention's d_prev of the NEXT position and
+ * the running d_cum.  Outputs: d_h [B,256] = d_q Wq (the query's gradient), d_q [B,A] (for dWq = sum over positions d_q^T h); ADDED in
+ * place: d_mem [B,Tk,A], and per-sequence partial sums dv_part [B,A], ddense_part [B,A,32], dconv_part [B,32,2,31] (mode 1) that the
+ * caller zeroes once and sums over B after the last position; mode 1 writes d_prev and d_cum [B,Tk] (row stride ldd), the gradients of
+ * the prev / cum inputs, d_cum += d_w_b when carry != 0 (the running sum: cum_i = cum_{i-1} + w_{i-1}).  Keys k >= lens[b]: enc, mem, prev,
+ * cum and the incoming gradients are never read, d_mem is not touched, d_prev / d_cum are exact zeros.  One workgroup per sequence, fp32
+ * FMAs, no atomics: two runs give the same bits.  ws: unast_rnn_attn_step_bwd_ws_floats(B, Tk, A) floats of scratch, 16-byte aligned.
+ * unast_lstm_cell_train: unast_lstm_cell's arithmetic (h and c_t carry its bits) from c_prev, storing saved [B,5,256] = (i, f, g, o, c_t)
+ * (row stride lds); hd (may be NULL) = h * mask, mask (may be NULL) a factor tensor (nn.LSTM's inter-layer dropout, src/module.py:350-351).
+ * unast_lstm_cell_bwd: dh_total = dh + dh2 * mask (each may be NULL), dc = dc_in + dh_total o (1 - tanh^2 c_t); dG [B,1024] = gradient of
+ * the gate pre-activations, dc_out = dc f (may be dc_in).  unast_tanh_bwd: dy *= 1 - y^2 in place (src/module.py:373's tanh). */
+int unast_rnn_attn_step_train(int mode, const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc,
+                              const int* lens, const float* prev_in, const float* cum_in, int ld_in, float* w_out, float* cum_out,
+                              int ld_out, const float* conv_w, const float* dense_w, float* ctx, int ldc, int B, int Tk, int A,
+                              hipStream_t stream);
+int64_t unast_rnn_attn_step_bwd_ws_floats(int B, int Tk, int A);
+int unast_rnn_attn_step_bwd(int mode, const float* d_ctx, int lddc, const float* w, const float* prev, const float* cum, int ldw,
+                            const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc, const int* lens,
+                            const float* conv_w, const float* dense_w, const float* d_w_a, const float* d_w_b, int carry, int ldd,
+                            float* d_h, int lddh, float* d_q, int lddq, float* d_mem, float* dv_part, float* ddense_part,
+                            float* dconv_part, float* d_prev, float* d_cum, float* ws, int64_t ws_floats, int B, int Tk, int A,
+                            hipStream_t stream);
+int unast_lstm_cell_train(const float* gates, int ldg, const float* c_prev, int ldcp, float* saved, int lds, float* h, int ldh,
+                          const float* mask, int ldm, float* hd, int ldhd, int B, int hidden, hipStream_t stream);
+int unast_lstm_cell_bwd(const float* dh, int lddh, const float* dh2, int lddh2, const float* mask, int ldm, const float* dc_in, int lddc,
+                        const float* saved, int lds, const float* c_prev, int ldcp, float* dG, int ldg, float* dc_out, int lddco, int B,
+                        int hidden, hipStream_t stream);
+int unast_tanh_bwd(float* dy, int lddy, const float* y, int ldy, int rows, int cols, hipStream_t stream);
 /* x = tanh(x) over [rows, cols]: the tanh behind RNNDecoder's linear_projection (src/module.py:373). */
 int unast_tanh_rows(float* x, int ldx, int rows, int cols, hipStream_t stream);
 /* TextRNN.decode's prenet input (src/network.py:573 runs TextPrenet over the whole prefix and keeps its last position, which depends on the

@@ -4,7 +4,10 @@ one decoded position eager and replayed for both models and both attention types
 encoder plus SpeechRNN.infer_sequence(max_len=frames); UNAST.tts itself always decodes up to infer_sequence's default of 815).
 Sizes: B = 32, T_text = 180, T_mel = 800.  --train: the encoder-training mode instead -- unast_lstm_seq_fwd_train next to unast_lstm_seq_fwd,
 unast_lstm_seq_bwd per recurrent step, and train_rnn.encoder_forward + encoder_backward of both models (dropout and noise on).
-Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train]"""
+--train-decoder: SpeechRNN decoder training at B = 32, T = 800, Tk in {180, 800}, both attention types (dropout on) -- decoder_forward,
+decoder_forward + decoder_backward, the per-position time of each loop (events recorded through the entry points' `mark` callback), the eval
+teacher-forced position of the same session as the yardstick, unast_rnn_attn_step_bwd next to unast_rnn_attn_step, and the saved-state bytes.
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder]"""
 import argparse
 import os
 import statistics
@@ -23,6 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--frames", type=int, default=800)
 ap.add_argument("--train", action="store_true")
+ap.add_argument("--train-decoder", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -86,8 +90,74 @@ def train_mode():
         print("%s encoder, B=%d T=%d, dropout and noise on: encoder_forward %.2f ms, encoder_forward + encoder_backward %.2f ms" % (name, B, T, fw, fb))
 
 
+def train_decoder_mode():
+    from unast_amd import train_rnn
+    g = torch.Generator().manual_seed(0)
+    _, mel, _, _ = (torch.from_numpy(x) for x in synth_batch(B, TT, TM, seed=3))
+    mel = mel.to(D)
+    M = mel.shape[2]
+    for attn in ("luong", "lsa"):
+        _, sm = models(attn)
+        mode = ops.ATTN_LSA if attn == "lsa" else ops.ATTN_LUONG
+        for Tk in (TT, TM):
+            enc = torch.randn(B, Tk, 512, generator=g).to(D) * 0.5
+            hc = (torch.randn(2, B, 256, generator=g).to(D) * 0.5, torch.randn(2, B, 256, generator=g).to(D) * 0.5)
+            lens_k = [Tk] * B
+            cot = (torch.randn(B, TM, M, device=D), torch.randn(B, TM, M, device=D), torch.randn(B, TM, device=D))
+            # the yardstick: the eval path's teacher-forced position, eager, same session
+            sm.eval()
+            with torch.no_grad():
+                gen = rnn.speech_generation(sm._pack(), (hc, enc), torch.tensor(lens_k, dtype=torch.int32, device=D), TM, target=mel)
+                gen.step(None)
+                gen.reset()
+                ev = median_ms(lambda: gen.step(None), inner=20)
+            sm.train()
+            keep = []
+            fw = median_ms(lambda: keep.__setitem__(slice(None), [train_rnn.decoder_forward(sm, mel, (hc, enc), lens_k, seed=3)]))
+            saved = keep[0].saved_bytes()
+            del keep[:]
+            loops = {"forward": [], "backward": []}
+
+            def marker(name):
+                def mark(_):
+                    e = torch.cuda.Event(enable_timing=True)
+                    e.record()
+                    loops[name].append(e)
+                return mark
+            fb = median_ms(lambda: train_rnn.decoder_backward(train_rnn.decoder_forward(sm, mel, (hc, enc), lens_k, seed=3, mark=marker("forward")), *cot,
+                                                              mark=marker("backward")))
+            per = {n: statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(0, len(ev), 2)) * 1e3 / TM for n, ev in loops.items()}
+            print("[%s] B=%d T=%d Tk=%d dropout on: decoder_forward %.1f ms, decoder_forward + decoder_backward %.1f ms; per position: forward loop %.1f us "
+                  "(eval teacher-forced position %.1f us, ratio %.2f), backward loop %.1f us; saved state %.1f MiB"
+                  % (attn, B, TM, Tk, fw, fb, per["forward"], ev * 1e3, per["forward"] / (ev * 1e3), per["backward"], saved / 2 ** 20))
+            # the attention kernels alone
+            P = train_rnn.decoder_pack_of(sm)
+            A = P.A
+            mem = torch.randn(B, Tk, A, generator=g).to(D) * 0.5
+            h = hc[0][1]
+            z = lambda *s: torch.zeros(*s, device=D)                                            # noqa: E731
+            prev, cum, ctx = torch.softmax(torch.randn(B, Tk, generator=g), 1).to(D), z(B, Tk), z(B, 512)
+            w, cum2 = z(B, Tk), z(B, Tk)
+            f_eval = median_ms(lambda: ops.rnn_attn_step(mode, h, P.Wq, mem, P.v, enc, gen.core.lens_k, ctx, prev=prev.clone(), cum=cum.clone(),
+                                                         conv_w=P.conv_w, dense_w=P.dense_w), inner=20)
+            f_train = median_ms(lambda: ops.rnn_attn_step_train(mode, h, P.Wq, mem, P.v, enc, gen.core.lens_k, ctx, w, prev_in=prev, cum_in=cum, cum_out=cum2,
+                                                                conv_w=P.conv_w, dense_w=P.dense_w), inner=20)
+            clone = median_ms(lambda: (prev.clone(), cum.clone()), inner=20)
+            ws = ops.rnn_attn_step_bwd_ws(B, Tk, A, D)
+            kw = dict(prev=prev, cum=cum, conv_w=P.conv_w, dense_w=P.dense_w, d_w_a=z(B, Tk), d_w_b=z(B, Tk), carry=True, ddense_part=z(B, A, 32),
+                      dconv_part=z(B, 32, 2, 31), d_prev=z(B, Tk), d_cum=z(B, Tk)) if attn == "lsa" else {}
+            d_h, d_q, d_mem, dv = z(B, 256), z(B, A), z(B, Tk, A), z(B, A)
+            bw = median_ms(lambda: ops.rnn_attn_step_bwd(mode, cot[0].new_ones(B, 512), w, h, P.Wq, mem, P.v, enc, gen.core.lens_k, d_h, d_q, d_mem, dv, ws, **kw),
+                           inner=20)
+            print("[%s] Tk=%d: unast_rnn_attn_step %.1f us (incl. %.1f us of two clones), unast_rnn_attn_step_train %.1f us, unast_rnn_attn_step_bwd %.1f us"
+                  % (attn, Tk, f_eval * 1e3, clone * 1e3, f_train * 1e3, bw * 1e3))
+
+
 if a.train:
     train_mode()
+    sys.exit(0)
+if a.train_decoder:
+    train_decoder_mode()
     sys.exit(0)
 
 with torch.no_grad():

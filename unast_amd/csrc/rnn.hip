@@ -1,9 +1,10 @@
 // Kernels of the RNN model family (TextRNN / SpeechRNN, src/network.py:279-402, 503-624; src/module.py:297-497) at the width every
-// full-size reference config uses, hidden 256: the eval path and the encoders' training (unast_amd/train_rnn.py).
+// full-size reference config uses, hidden 256: the eval path, the encoders' training and the SpeechRNN decoder's (unast_amd/train_rnn.py).
 //   lstm_seq_fwd_kernel   recurrence of one packed nn.LSTM layer (src/module.py:306, 315-317); <true> also saves what the backward reads
 //   lstm_seq_bwd_kernel   backpropagation through time of that recurrence
 //   rnn_attn_step_kernel  one step of Luong / location-sensitive additive attention (src/module.py:395-497)
 //   lstm_cell_kernel      pointwise cell update of one decoder step (the nn.LSTM call of src/module.py:371 at sequence length 1)
+//   rnn_attn_step_bwd_kernel, lstm_cell_train_kernel, lstm_cell_bwd_kernel, tanh_bwd_kernel   one position of the decoder's training loops
 #include "common.h"
 
 namespace {
@@ -355,11 +356,16 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 // One workgroup per sequence.  LDS (dynamic, floats): qp[64] | vs[64] | red[4 + 12 pad] | sc[Tk4] and, in LSA mode, behind them
 // pc[2][Tk4 + 32] (prev and cum with a zero halo of 15 on the left and at least 15 on the right) | conv[32*2*31] | dense[A*32].
+// TRAIN (unast_rnn_attn_step_train): the same instructions on ctx and the weights, out of place -- prev / cum are read from prev_in / cum_in
+// (row stride ld_in) and the weights / cum + weights written to prev / cum (row stride ld_out); <false> ignores those three arguments.
+template <bool TRAIN>
 __global__ __launch_bounds__(ATT_THREADS) void rnn_attn_step_kernel(int mode, const float* __restrict__ hq, int ldq, const float* __restrict__ Wq,
                                                                     const float* __restrict__ mem, const float* __restrict__ vw,
                                                                     const float* __restrict__ enc, const int* __restrict__ lens, float* __restrict__ prev,
                                                                     float* __restrict__ cum, const float* __restrict__ conv_w,
-                                                                    const float* __restrict__ dense_w, float* __restrict__ ctx, int ldc, int Tk, int A) {
+                                                                    const float* __restrict__ dense_w, float* __restrict__ ctx, int ldc, int Tk, int A,
+                                                                    const float* __restrict__ prev_in, const float* __restrict__ cum_in, int ld_in,
+                                                                    int ld_out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Tk4 = (Tk + 3) & ~3;
     float* qp = smem;
@@ -386,7 +392,8 @@ __global__ __launch_bounds__(ATT_THREADS) void rnn_attn_step_kernel(int mode, co
     if (mode == 1) {
         for (int i = tid; i < 2 * ldp; i += ATT_THREADS) {
             const int ch = i / ldp, t = i - ch * ldp - LOC_PAD;
-            pc[i] = (t >= 0 && t < Tk) ? (ch ? cum : prev)[(size_t)b * Tk + t] : 0.f;
+            if constexpr (TRAIN) pc[i] = (t >= 0 && t < Tk) ? (ch ? cum_in : prev_in)[(size_t)b * ld_in + t] : 0.f;
+            else pc[i] = (t >= 0 && t < Tk) ? (ch ? cum : prev)[(size_t)b * Tk + t] : 0.f;
         }
         for (int i = tid; i < LOC_F * 2 * LOC_K; i += ATT_THREADS) convs[i] = conv_w[i];
         for (int i = tid; i < A * LOC_F; i += ATT_THREADS) denses[i] = dense_w[i];
@@ -435,8 +442,13 @@ __global__ __launch_bounds__(ATT_THREADS) void rnn_attn_step_kernel(int mode, co
     for (int t = tid; t < Tk; t += ATT_THREADS) {
         const float w = t < len ? sc[t] * inv : 0.f;                // masked keys: exactly zero
         if (t < len) sc[t] = w;
-        if (prev) prev[(size_t)b * Tk + t] = w;
-        if (mode == 1) cum[(size_t)b * Tk + t] = pc[ldp + LOC_PAD + t] + w;
+        if constexpr (TRAIN) {
+            prev[(size_t)b * ld_out + t] = w;
+            if (mode == 1) cum[(size_t)b * ld_out + t] = pc[ldp + LOC_PAD + t] + w;
+        } else {
+            if (prev) prev[(size_t)b * Tk + t] = w;
+            if (mode == 1) cum[(size_t)b * Tk + t] = pc[ldp + LOC_PAD + t] + w;
+        }
     }
     __syncthreads();
 
@@ -471,6 +483,282 @@ __global__ void lstm_cell_kernel(const float* __restrict__ gates, int ldg, float
     c[(size_t)b * ldcs + u] = cn;
     h[(size_t)b * ldh + u] = og * tanhf(cn);
 }
+
+// ---- decoder training: what unast_amd.train_rnn.decoder_forward / decoder_backward launch per position -------------------------------------
+// lstm_cell_kernel's arithmetic (the same expressions, so h and c_t carry its bits) out of place, storing what the backward reads:
+// saved[b] = (i, f, g, o, c_t) as [5,256].  hd != NULL: a second copy of h for the next layer, times mask (nn.LSTM's inter-layer dropout as a
+// factor tensor, 0 or 1/(1-p)) when there is one; the carried h stays undropped.
+__global__ void lstm_cell_train_kernel(const float* __restrict__ gates, int ldg, const float* __restrict__ cprev, int ldcp, float* __restrict__ saved,
+                                       int lds, float* __restrict__ h, int ldh, const float* __restrict__ mask, int ldm, float* __restrict__ hd, int ldhd,
+                                       int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * RH) return;
+    const int b = i / RH, u = i - b * RH;
+    const float* g = gates + (size_t)b * ldg + u;
+    const float ig = sigmoidf_(g[0]), fg = sigmoidf_(g[RH]), gg = tanhf(g[2 * RH]), og = sigmoidf_(g[3 * RH]);
+    const float cn = fg * cprev[(size_t)b * ldcp + u] + ig * gg;
+    float* s = saved + (size_t)b * lds + u;
+    s[0] = ig; s[RH] = fg; s[2 * RH] = gg; s[3 * RH] = og; s[4 * RH] = cn;
+    const float hn = og * tanhf(cn);
+    h[(size_t)b * ldh + u] = hn;
+    if (hd) hd[(size_t)b * ldhd + u] = mask ? hn * mask[(size_t)b * ldm + u] : hn;
+}
+
+// Backward of one cell update: dh_total = dh + dh2 (* mask), dc = dc_in + dh_total o (1 - tanh(c_t)^2) with tanh(c_t) recomputed;
+// dG [B,1024] = gradient of the gate pre-activations, dc_out = dc f (dc_out may be dc_in: one thread reads and writes an element).
+__global__ void lstm_cell_bwd_kernel(const float* __restrict__ dh, int lddh, const float* __restrict__ dh2, int lddh2, const float* __restrict__ mask,
+                                     int ldm, const float* dc_in, int lddc, const float* __restrict__ saved, int lds,
+                                     const float* __restrict__ cprev, int ldcp, float* __restrict__ dG, int ldg, float* dc_out, int lddco, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * RH) return;
+    const int b = i / RH, u = i - b * RH;
+    float d = dh ? dh[(size_t)b * lddh + u] : 0.f;
+    if (dh2) {
+        const float e = dh2[(size_t)b * lddh2 + u];
+        d += mask ? e * mask[(size_t)b * ldm + u] : e;
+    }
+    const float* s = saved + (size_t)b * lds + u;
+    const float ig = s[0], fg = s[RH], gg = s[2 * RH], og = s[3 * RH], tc = tanhf(s[4 * RH]);
+    const float dc = (dc_in ? dc_in[(size_t)b * lddc + u] : 0.f) + d * og * (1.f - tc * tc);
+    float* o = dG + (size_t)b * ldg + u;
+    o[0] = dc * gg * ig * (1.f - ig);
+    o[RH] = dc * cprev[(size_t)b * ldcp + u] * fg * (1.f - fg);
+    o[2 * RH] = dc * ig * (1.f - gg * gg);
+    o[3 * RH] = d * tc * og * (1.f - og);
+    dc_out[(size_t)b * lddco + u] = dc * fg;
+}
+
+// dy *= 1 - y^2 in place: backward of y = tanh(.) from the stored output.
+__global__ void tanh_bwd_kernel(float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int rows, int cols) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * cols) return;
+    const int r = i / cols, c = i - r * cols;
+    const float t = y[(size_t)r * ldy + c];
+    dy[(size_t)r * lddy + c] *= 1.f - t * t;
+}
+
+// Backward of one rnn_attn_step_kernel position, the same decomposition: one workgroup per sequence, fp32 on the vector ALUs, no atomics and
+// no workgroup waits on another, so two runs give the same bits.  Everything a sequence's workgroup adds to (d_mem[b], the per-sequence partial
+// sums of d_v, d_dense and d_conv_w) is owned by it; the partial sums are reduced over b after the loop in a fixed order.
+//   dw[t]   = dwa[t] + dwb[t] + enc[b,t] . d_ctx[b]                  (t < len; the incoming gradient of the weights: LSA's d_prev of the next
+//                                                                     position and the running d_cum)
+//   de[t]   = w[t] (dw[t] - sum_s w[s] dw[s])                         softmax backward over the live keys (masked keys: w = 0, no gradient)
+//   dx[t,a] = de[t] v[a] (1 - th^2), th = tanh(qp[a] + loc[t,a] + mem[b,t,a]) recomputed with the forward's expressions
+//   d_q[a] = sum_t dx[t,a], d_h = d_q Wq, d_mem[b,t,:] += dx[t,:], d_v[a] += sum_t de[t] th[t,a]
+//   LSA: F[t,f] = conv(prev, cum)[t,f] recomputed, dF[t,f] = sum_a dx[t,a] dense[a,f]; d_dense[a,f] += sum_t dx[t,a] F[t,f];
+//        d_conv[f,ch,k] += sum_t dF[t,f] in[ch][t+k-15]; d_in[ch][s] = sum_{f,k} conv[f,ch,k] dF[s-k+15,f] (transposed conv, zero halo).
+// Keys t >= len: enc, mem, prev, cum, dwa and dwb are never read there; d_prev / d_cum are written as exact zeros, d_mem is not touched.
+// LDS (floats): qp[64] | vs[64] | red[16] | sdq[64] | part[4*2*64] | sdc[512] | sdw[Tk4] | sw[Tk4] and in LSA mode pc[2][Tk4+32] | conv[1984] |
+// dense[A*32].  ws (global, per sequence Tk*(64+2A) floats, L2-resident): F | dF | dx | u = de th, written by the thread that owns key t and
+// read by all after a barrier (phase 3: a thread owns a few output elements and makes one pass over the keys).
+__global__ __launch_bounds__(ATT_THREADS) void rnn_attn_step_bwd_kernel(
+    int mode, const float* __restrict__ dctx, int lddc, const float* __restrict__ w, const float* __restrict__ prev, const float* __restrict__ cum, int ldw,
+    const float* __restrict__ hq, int ldq, const float* __restrict__ Wq, const float* __restrict__ mem, const float* __restrict__ vw,
+    const float* __restrict__ enc, const int* __restrict__ lens, const float* __restrict__ conv_w, const float* __restrict__ dense_w,
+    const float* __restrict__ dwa, const float* __restrict__ dwb, int carry, int ldd, float* __restrict__ dh, int lddh, float* __restrict__ dq, int lddq,
+    float* dmem, float* __restrict__ dv_part, float* __restrict__ ddense_part, float* __restrict__ dconv_part, float* __restrict__ dprev,
+    float* __restrict__ dcum, float* ws, int Tk, int A) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Tk4 = (Tk + 3) & ~3;
+    float* qp = smem;
+    float* vs = qp + ATT_MAX_A;
+    float* red = vs + ATT_MAX_A;
+    float* sdq = red + 16;
+    float* part = sdq + ATT_MAX_A;
+    float* sdc = part + 8 * 64;
+    float* sdw = sdc + ENC_D;
+    float* sw = sdw + Tk4;
+    float* pc = sw + Tk4;
+    const int ldp = Tk4 + 32;
+    float* convs = pc + 2 * ldp;
+    float* denses = convs + LOC_F * 2 * LOC_K;
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int len = min(max(lens[b], 0), Tk);
+
+    {   // the forward's query-side projection, instruction for instruction
+        const float4 hv = *reinterpret_cast<const float4*>(hq + (size_t)b * ldq + lane * 4);
+        for (int a = wave; a < A; a += ATT_THREADS / 64) {
+            const float4 wv = *reinterpret_cast<const float4*>(Wq + (size_t)a * RH + lane * 4);
+            const float s = wave_sum((wv.x * hv.x + wv.y * hv.y) + (wv.z * hv.z + wv.w * hv.w));
+            if (lane == 0) qp[a] = s;
+        }
+    }
+    if (tid < A) vs[tid] = vw[tid];
+    sdc[tid] = dctx[(size_t)b * lddc + tid];
+    sdc[tid + ATT_THREADS] = dctx[(size_t)b * lddc + tid + ATT_THREADS];
+    for (int t = tid; t < Tk4; t += ATT_THREADS) sw[t] = t < len ? w[(size_t)b * ldw + t] : 0.f;
+    if (mode == 1) {
+        for (int i = tid; i < 2 * ldp; i += ATT_THREADS) {
+            const int ch = i / ldp, t = i - ch * ldp - LOC_PAD;
+            pc[i] = (t >= 0 && t < len) ? (ch ? cum : prev)[(size_t)b * ldw + t] : 0.f;      // (the forward's weights are exact zeros at t >= len)
+        }
+        for (int i = tid; i < LOC_F * 2 * LOC_K; i += ATT_THREADS) convs[i] = conv_w[i];
+        for (int i = tid; i < A * LOC_F; i += ATT_THREADS) denses[i] = dense_w[i];
+    }
+    __syncthreads();
+
+    // phase 1: dw[t] = incoming + enc[b,t] . d_ctx[b], a wave per key row (2 KiB contiguous)
+    {
+        const float4 c0 = reinterpret_cast<const float4*>(sdc)[lane], c1 = reinterpret_cast<const float4*>(sdc)[64 + lane];
+        for (int t0 = wave; t0 < len; t0 += 4 * (ATT_THREADS / 64)) {                        // four rows in flight per wave
+            float s[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + u * (ATT_THREADS / 64);
+                s[u] = 0.f;
+                if (t < len) {
+                    const float4* e = reinterpret_cast<const float4*>(enc + ((size_t)b * Tk + t) * ENC_D);
+                    const float4 e0 = e[lane], e1 = e[64 + lane];
+                    s[u] = ((e0.x * c0.x + e0.y * c0.y) + (e0.z * c0.z + e0.w * c0.w)) + ((e1.x * c1.x + e1.y * c1.y) + (e1.z * c1.z + e1.w * c1.w));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[u] = wave_sum(s[u]);
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int t = t0 + u * (ATT_THREADS / 64);
+                    if (t < len) {
+                        float v = s[u];
+                        if (dwa) v += dwa[(size_t)b * ldd + t];
+                        if (dwb) v += dwb[(size_t)b * ldd + t];
+                        sdw[t] = v;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float dot = 0.f;
+    for (int t = tid; t < len; t += ATT_THREADS) dot = fmaf(sw[t], sdw[t], dot);
+    dot = block_sum(dot, red);
+    for (int t = tid; t < len; t += ATT_THREADS) sdw[t] = sw[t] * (sdw[t] - dot);          // de[t]; each thread keeps to its own keys below
+
+    // phase 2: a thread per key: tanh argument recomputed, dx / u / F / dF to the workspace, d_mem += dx
+    const size_t wsb = (size_t)Tk * (2 * LOC_F + 2 * A);
+    float* wsF = ws + (size_t)b * wsb;
+    float* wsdF = wsF + (size_t)Tk * LOC_F;
+    float* wsdx = wsdF + (size_t)Tk * LOC_F;
+    float* wsu = wsdx + (size_t)Tk * A;
+    for (int t = tid; t < len; t += ATT_THREADS) {
+        float f[LOC_F], df[LOC_F];
+        if (mode == 1) {
+#pragma unroll
+            for (int i = 0; i < LOC_F; ++i) { f[i] = 0.f; df[i] = 0.f; }
+            for (int ch = 0; ch < 2; ++ch)
+                for (int k = 0; k < LOC_K; ++k) {
+                    const float x = pc[ch * ldp + t + k];
+#pragma unroll
+                    for (int i = 0; i < LOC_F; ++i) f[i] = fmaf(convs[(i * 2 + ch) * LOC_K + k], x, f[i]);
+                }
+        }
+        const float de = sdw[t];
+        const float* mrow = mem + ((size_t)b * Tk + t) * A;
+        float* dmrow = dmem + ((size_t)b * Tk + t) * A;
+        for (int a = 0; a < A; ++a) {
+            float x = qp[a];
+            if (mode == 1) {
+                float loc = 0.f;
+#pragma unroll
+                for (int i = 0; i < LOC_F; ++i) loc = fmaf(denses[a * LOC_F + i], f[i], loc);
+                x += loc;
+            }
+            x += mrow[a];
+            const float th = tanhf(x);
+            const float dxv = de * vs[a] * (1.f - th * th);
+            wsu[(size_t)t * A + a] = de * th;
+            wsdx[(size_t)t * A + a] = dxv;
+            dmrow[a] += dxv;
+            if (mode == 1) {
+#pragma unroll
+                for (int i = 0; i < LOC_F; ++i) df[i] = fmaf(dxv, denses[a * LOC_F + i], df[i]);
+            }
+        }
+        if (mode == 1) {
+#pragma unroll
+            for (int i = 0; i < LOC_F; ++i) { wsF[(size_t)t * LOC_F + i] = f[i]; wsdF[(size_t)t * LOC_F + i] = df[i]; }
+        }
+    }
+    __syncthreads();
+
+    // phase 3: d_q and d_v: wave w sums the keys t = w (mod 4), lane = a; the four partial sums are combined in a fixed order
+    if (lane < A) {
+        float sq = 0.f, sv = 0.f;
+#pragma unroll 4
+        for (int t = wave; t < len; t += ATT_THREADS / 64) { sq += wsdx[(size_t)t * A + lane]; sv += wsu[(size_t)t * A + lane]; }
+        part[(wave * 2 + 0) * 64 + lane] = sq;
+        part[(wave * 2 + 1) * 64 + lane] = sv;
+    }
+    __syncthreads();
+    if (tid < A) {
+        const float q = (part[0 * 64 + tid] + part[2 * 64 + tid]) + (part[4 * 64 + tid] + part[6 * 64 + tid]);
+        sdq[tid] = q;
+        dq[(size_t)b * lddq + tid] = q;
+        dv_part[(size_t)b * A + tid] += (part[1 * 64 + tid] + part[3 * 64 + tid]) + (part[5 * 64 + tid] + part[7 * 64 + tid]);
+    }
+    __syncthreads();
+    {   // d_h[b, j] = sum_a d_q[a] Wq[a, j]
+        float s = 0.f;
+        for (int a = 0; a < A; ++a) s = fmaf(sdq[a], Wq[(size_t)a * RH + tid], s);
+        dh[(size_t)b * lddh + tid] = s;
+    }
+    if (mode != 1) return;
+    {   // d_dense[a, f] += sum_t dx[t,a] F[t,f]: lane = f, a thread owns a = tid / 32 + 8 r; one pass over the keys for all its outputs
+        const int fi = tid & 31, a0 = tid >> 5;
+        float acc[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+#pragma unroll 2
+        for (int t = 0; t < len; ++t) {
+            const float fv = wsF[(size_t)t * LOC_F + fi];
+            const float* dxr = wsdx + (size_t)t * A;
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (a0 + 8 * r < A) acc[r] = fmaf(dxr[a0 + 8 * r], fv, acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+            if (a0 + 8 * r < A) ddense_part[((size_t)b * A + a0 + 8 * r) * LOC_F + fi] += acc[r];
+    }
+    {   // d_conv[f, ch, k] += sum_t dF[t,f] in[ch][t+k-15]: lane = (ch, k) (62 of 64), a thread owns f = tid / 64 + 4 r
+        const int j = tid & 63, fg = tid >> 6;
+        if (j < 2 * LOC_K) {
+            const int ch = j / LOC_K, k = j - ch * LOC_K;
+            const float* pin = pc + ch * ldp + k;
+            float acc[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+#pragma unroll 2
+            for (int t = 0; t < len; ++t) {
+                const float x = pin[t];
+                const float* dfr = wsdF + (size_t)t * LOC_F + fg;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) acc[r] = fmaf(dfr[4 * r], x, acc[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) dconv_part[((size_t)b * LOC_F + fg + 4 * r) * 2 * LOC_K + j] += acc[r];
+        }
+    }
+    for (int s_ = tid; s_ < Tk; s_ += ATT_THREADS) {
+        float a0 = 0.f, a1 = 0.f;
+        if (s_ < len) {
+            for (int k = 0; k < LOC_K; ++k) {
+                const int t = s_ - k + LOC_PAD;
+                if (t < 0 || t >= len) continue;
+                const float* row = wsdF + (size_t)t * LOC_F;
+#pragma unroll
+                for (int i = 0; i < LOC_F; ++i) {
+                    a0 = fmaf(convs[(i * 2 + 0) * LOC_K + k], row[i], a0);
+                    a1 = fmaf(convs[(i * 2 + 1) * LOC_K + k], row[i], a1);
+                }
+            }
+            if (carry && dwb) a1 += dwb[(size_t)b * ldd + s_];
+        }
+        dprev[(size_t)b * ldd + s_] = a0;
+        dcum[(size_t)b * ldd + s_] = a1;
+    }
+}
+
 
 __global__ void tanh_rows_kernel(float* __restrict__ x, int ldx, int rows, int cols) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -615,8 +903,8 @@ extern "C" int unast_rnn_attn_step(int mode, const float* h, int ldh, const floa
     const int Tk4 = (Tk + 3) & ~3;
     size_t fl = 2 * ATT_MAX_A + 16 + Tk4;
     if (mode == 1) fl += 2 * (size_t)(Tk4 + 32) + LOC_F * 2 * LOC_K + (size_t)A * LOC_F;
-    hipLaunchKernelGGL(rnn_attn_step_kernel, dim3(B), dim3(ATT_THREADS), fl * sizeof(float), stream, mode, h, ldh, Wq, mem, v, enc, lens, prev, cum,
-                       conv_w, dense_w, ctx, ldc, Tk, A);
+    hipLaunchKernelGGL(rnn_attn_step_kernel<false>, dim3(B), dim3(ATT_THREADS), fl * sizeof(float), stream, mode, h, ldh, Wq, mem, v, enc, lens, prev, cum,
+                       conv_w, dense_w, ctx, ldc, Tk, A, (const float*)nullptr, (const float*)nullptr, 0, 0);
     return unast_check_launch("unast_rnn_attn_step");
 }
 
@@ -626,6 +914,93 @@ extern "C" int unast_lstm_cell(const float* gates, int ldg, float* c, int ldc, f
     UNAST_REQUIRE(B > 0 && ldg >= RG && ldc >= RH && ldh >= RH, "unast_lstm_cell: bad dims");
     hipLaunchKernelGGL(lstm_cell_kernel, dim3((B * RH + 255) / 256), dim3(256), 0, stream, gates, ldg, c, ldc, h, ldh, B);
     return unast_check_launch("unast_lstm_cell");
+}
+
+extern "C" int unast_rnn_attn_step_train(int mode, const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc,
+                                         const int* lens, const float* prev_in, const float* cum_in, int ld_in, float* w_out, float* cum_out,
+                                         int ld_out, const float* conv_w, const float* dense_w, float* ctx, int ldc, int B, int Tk, int A,
+                                         hipStream_t stream) {
+    UNAST_REQUIRE(mode == 0 || mode == 1, "unast_rnn_attn_step_train: mode 0 (Luong) or 1 (location-sensitive), got %d", mode);
+    UNAST_REQUIRE(h && Wq && mem && v && enc && lens && ctx && w_out, "unast_rnn_attn_step_train: null pointer");
+    UNAST_REQUIRE(mode == 0 || (prev_in && cum_in && cum_out && conv_w && dense_w),
+                  "unast_rnn_attn_step_train: mode 1 needs prev_in, cum_in, cum_out and the location layer's weights");
+    UNAST_REQUIRE(B > 0 && Tk > 0 && Tk <= 2048, "unast_rnn_attn_step_train: B=%d, Tk=%d (1..2048: a sequence's keys are staged in LDS)", B, Tk);
+    UNAST_REQUIRE(A > 0 && A <= ATT_MAX_A && A % 4 == 0, "unast_rnn_attn_step_train: attn_dim must be a multiple of 4, at most %d (got %d)", ATT_MAX_A, A);
+    UNAST_REQUIRE(ldh >= RH && ldh % 4 == 0 && ldc >= ENC_D && ldc % 2 == 0 && ld_out >= Tk && (mode == 0 || ld_in >= Tk),
+                  "unast_rnn_attn_step_train: bad row strides");
+    UNAST_REQUIRE(mode == 0 || (w_out != prev_in && w_out != cum_in && cum_out != cum_in && cum_out != prev_in && w_out != cum_out),
+                  "unast_rnn_attn_step_train: the outputs must not be the inputs (out of place; unast_rnn_attn_step is the in-place form)");
+    UNAST_REQUIRE(((((uintptr_t)h) | ((uintptr_t)Wq)) & 15) == 0 && ((((uintptr_t)enc) | ((uintptr_t)ctx)) & 7) == 0,
+                  "unast_rnn_attn_step_train: h and Wq must be 16-byte aligned, enc and ctx 8-byte aligned");
+    const int Tk4 = (Tk + 3) & ~3;
+    size_t fl = 2 * ATT_MAX_A + 16 + Tk4;
+    if (mode == 1) fl += 2 * (size_t)(Tk4 + 32) + LOC_F * 2 * LOC_K + (size_t)A * LOC_F;
+    hipLaunchKernelGGL(rnn_attn_step_kernel<true>, dim3(B), dim3(ATT_THREADS), fl * sizeof(float), stream, mode, h, ldh, Wq, mem, v, enc, lens, w_out,
+                       cum_out, conv_w, dense_w, ctx, ldc, Tk, A, prev_in, cum_in, ld_in, ld_out);
+    return unast_check_launch("unast_rnn_attn_step_train");
+}
+
+extern "C" int64_t unast_rnn_attn_step_bwd_ws_floats(int B, int Tk, int A) {
+    if (B <= 0 || Tk <= 0 || A <= 0) return 0;
+    return (int64_t)B * Tk * (2 * LOC_F + 2 * A);
+}
+
+extern "C" int unast_rnn_attn_step_bwd(int mode, const float* d_ctx, int lddc, const float* w, const float* prev, const float* cum, int ldw,
+                                       const float* h, int ldh, const float* Wq, const float* mem, const float* v, const float* enc, const int* lens,
+                                       const float* conv_w, const float* dense_w, const float* d_w_a, const float* d_w_b, int carry, int ldd,
+                                       float* d_h, int lddh, float* d_q, int lddq, float* d_mem, float* dv_part, float* ddense_part,
+                                       float* dconv_part, float* d_prev, float* d_cum, float* ws, int64_t ws_floats, int B, int Tk, int A,
+                                       hipStream_t stream) {
+    UNAST_REQUIRE(mode == 0 || mode == 1, "unast_rnn_attn_step_bwd: mode 0 (Luong) or 1 (location-sensitive), got %d", mode);
+    UNAST_REQUIRE(d_ctx && w && h && Wq && mem && v && enc && lens && d_h && d_q && d_mem && dv_part && ws, "unast_rnn_attn_step_bwd: null pointer");
+    UNAST_REQUIRE(mode == 0 || (prev && cum && conv_w && dense_w && ddense_part && dconv_part && d_prev && d_cum),
+                  "unast_rnn_attn_step_bwd: mode 1 needs prev, cum, the location layer's weights, their partial sums, d_prev and d_cum");
+    UNAST_REQUIRE(B > 0 && Tk > 0 && Tk <= 2048, "unast_rnn_attn_step_bwd: B=%d, Tk=%d (1..2048: a sequence's keys are staged in LDS)", B, Tk);
+    UNAST_REQUIRE(A > 0 && A <= ATT_MAX_A && A % 4 == 0, "unast_rnn_attn_step_bwd: attn_dim must be a multiple of 4, at most %d (got %d)", ATT_MAX_A, A);
+    UNAST_REQUIRE(ldh >= RH && ldh % 4 == 0 && lddc >= ENC_D && ldw >= Tk && lddh >= RH && lddq >= A && ((!d_w_a && !d_w_b && mode == 0) || ldd >= Tk),
+                  "unast_rnn_attn_step_bwd: bad row strides");
+    UNAST_REQUIRE(((((uintptr_t)h) | ((uintptr_t)Wq) | ((uintptr_t)enc) | ((uintptr_t)ws)) & 15) == 0,
+                  "unast_rnn_attn_step_bwd: h, Wq, enc and ws must be 16-byte aligned");
+    UNAST_REQUIRE(ws_floats >= unast_rnn_attn_step_bwd_ws_floats(B, Tk, A), "unast_rnn_attn_step_bwd: workspace too small (%lld floats)", (long long)ws_floats);
+    UNAST_REQUIRE(mode == 0 || ((d_prev != d_w_a) && (d_cum != d_w_b) && (d_prev != d_w_b) && (d_cum != d_w_a) && d_prev != d_cum),
+                  "unast_rnn_attn_step_bwd: d_prev / d_cum must not be the incoming buffers (keys are read by other threads than write them)");
+    const int Tk4 = (Tk + 3) & ~3;
+    size_t fl = 3 * ATT_MAX_A + 16 + 8 * 64 + ENC_D + 2 * (size_t)Tk4;
+    if (mode == 1) fl += 2 * (size_t)(Tk4 + 32) + LOC_F * 2 * LOC_K + (size_t)A * LOC_F;
+    hipLaunchKernelGGL(rnn_attn_step_bwd_kernel, dim3(B), dim3(ATT_THREADS), fl * sizeof(float), stream, mode, d_ctx, lddc, w, prev, cum, ldw, h, ldh, Wq, mem,
+                       v, enc, lens, conv_w, dense_w, d_w_a, d_w_b, carry, ldd, d_h, lddh, d_q, lddq, d_mem, dv_part, ddense_part, dconv_part, d_prev,
+                       d_cum, ws, Tk, A);
+    return unast_check_launch("unast_rnn_attn_step_bwd");
+}
+
+extern "C" int unast_lstm_cell_train(const float* gates, int ldg, const float* c_prev, int ldcp, float* saved, int lds, float* h, int ldh,
+                                     const float* mask, int ldm, float* hd, int ldhd, int B, int hidden, hipStream_t stream) {
+    UNAST_REQUIRE(gates && c_prev && saved && h, "unast_lstm_cell_train: null pointer");
+    UNAST_REQUIRE(hidden == RH, "unast_lstm_cell_train: built for hidden=%d only (got %d)", RH, hidden);
+    UNAST_REQUIRE(B > 0 && ldg >= RG && ldcp >= RH && lds >= 5 * RH && ldh >= RH && (!hd || ldhd >= RH) && (!mask || (hd && ldm >= RH)),
+                  "unast_lstm_cell_train: bad dims (a mask needs hd)");
+    hipLaunchKernelGGL(lstm_cell_train_kernel, dim3((B * RH + 255) / 256), dim3(256), 0, stream, gates, ldg, c_prev, ldcp, saved, lds, h, ldh, mask, ldm, hd,
+                       ldhd, B);
+    return unast_check_launch("unast_lstm_cell_train");
+}
+
+extern "C" int unast_lstm_cell_bwd(const float* dh, int lddh, const float* dh2, int lddh2, const float* mask, int ldm, const float* dc_in, int lddc,
+                                   const float* saved, int lds, const float* c_prev, int ldcp, float* dG, int ldg, float* dc_out, int lddco, int B,
+                                   int hidden, hipStream_t stream) {
+    UNAST_REQUIRE(saved && c_prev && dG && dc_out, "unast_lstm_cell_bwd: null pointer");
+    UNAST_REQUIRE(hidden == RH, "unast_lstm_cell_bwd: built for hidden=%d only (got %d)", RH, hidden);
+    UNAST_REQUIRE(B > 0 && ldg >= RG && ldcp >= RH && lds >= 5 * RH && lddco >= RH && (!dh || lddh >= RH) && (!dh2 || lddh2 >= RH) &&
+                      (!mask || (dh2 && ldm >= RH)) && (!dc_in || lddc >= RH),
+                  "unast_lstm_cell_bwd: bad dims (a mask needs dh2)");
+    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3((B * RH + 255) / 256), dim3(256), 0, stream, dh, lddh, dh2, lddh2, mask, ldm, dc_in, lddc, saved, lds,
+                       c_prev, ldcp, dG, ldg, dc_out, lddco, B);
+    return unast_check_launch("unast_lstm_cell_bwd");
+}
+
+extern "C" int unast_tanh_bwd(float* dy, int lddy, const float* y, int ldy, int rows, int cols, hipStream_t stream) {
+    UNAST_REQUIRE(dy && y && rows > 0 && cols > 0 && lddy >= cols && ldy >= cols && (long long)rows * cols <= 0x7FFFFFFF, "unast_tanh_bwd: bad arguments");
+    hipLaunchKernelGGL(tanh_bwd_kernel, dim3((rows * cols + 255) / 256), dim3(256), 0, stream, dy, lddy, y, ldy, rows, cols);
+    return unast_check_launch("unast_tanh_bwd");
 }
 
 extern "C" int unast_tanh_rows(float* x, int ldx, int rows, int cols, hipStream_t stream) {

@@ -933,6 +933,149 @@ def lstm_cell(gates, c, h):
     return h
 
 
+# ---- SpeechRNN decoder training (csrc/rnn.hip; unast_amd/train_rnn.py) -------------------------------------------------------------------
+def _rows(t, name, B, cols, align=1):
+    """A [B, cols] float32 view with unit column stride (a position's slice of a [B,T,...] slab); returns its row stride."""
+    _f32(t, name)
+    if t.dim() != 2 or tuple(t.shape) != (B, cols) or t.stride(1) != 1 or t.stride(0) < cols or t.stride(0) % align or t.data_ptr() % (4 * align):
+        raise ValueError("%s must be [%d,%d] with unit column stride%s (got shape %s, strides %s)"
+                         % (name, B, cols, " and %d-byte aligned rows" % (4 * align) if align > 1 else "", tuple(t.shape), t.stride()))
+    return t.stride(0)
+
+
+def _attn_operands(name, h, Wq, mem, v, enc, lens_i32):
+    if mem.dim() != 3 or enc.dim() != 3:
+        raise ValueError("%s: mem [B,Tk,A] and enc [B,Tk,512]" % name)
+    B, Tk, A = mem.shape
+    if A % 4 or A > 64 or A < 4:
+        raise ValueError("%s: attn_dim must be a multiple of 4, at most 64 (got %d)" % (name, A))
+    if not 1 <= Tk <= 2048:
+        raise ValueError("%s: 1 <= Tk <= 2048 (got %d)" % (name, Tk))
+    _dense_f32(mem, "mem")
+    _dense_f32(enc, "enc", (B, Tk, 512))
+    _dense_f32(Wq, "Wq", (A, 256))
+    _f32(v, "v")
+    if not v.is_contiguous() or v.numel() != A:
+        raise ValueError("%s: v must hold A contiguous floats" % name)
+    _rows(h, "h", B, 256, 4)
+    if not (lens_i32.is_cuda and lens_i32.dtype == torch.int32 and lens_i32.is_contiguous() and lens_i32.numel() == B):
+        raise TypeError("%s: lens must be a contiguous int32 CUDA tensor [B]" % name)
+    return B, Tk, A
+
+
+def _same_stride(name, B, Tk, *named):
+    ld = None
+    for t, n in named:
+        if t is None:
+            continue
+        s = _rows(t, n, B, Tk)
+        if ld is not None and s != ld:
+            raise ValueError("%s: %s must share one row stride (got %d and %d)" % (name, " / ".join(n for _, n in named), ld, s))
+        ld = s
+    return ld or 0
+
+
+def rnn_attn_step_train(mode, h, Wq, mem, v, enc, lens_i32, ctx, w_out, prev_in=None, cum_in=None, cum_out=None, conv_w=None, dense_w=None):
+    """rnn_attn_step out of place (ctx and the weights carry its bits): the weights go to w_out [B,Tk]; LSA mode reads prev_in / cum_in and
+    writes cum_in + weights to cum_out.  All [B,Tk] operands are row-strided views (prev_in / cum_in share a stride, w_out / cum_out another)."""
+    if mode not in (ATTN_LUONG, ATTN_LSA):
+        raise ValueError("rnn_attn_step_train: mode must be ATTN_LUONG (0) or ATTN_LSA (1), got %r" % (mode,))
+    B, Tk, A = _attn_operands("rnn_attn_step_train", h, Wq, mem, v, enc, lens_i32)
+    ldc = _rows(ctx, "ctx", B, 512, 2)
+    if mode == ATTN_LSA:
+        if prev_in is None or cum_in is None or cum_out is None or conv_w is None or dense_w is None:
+            raise ValueError("rnn_attn_step_train: LSA mode needs prev_in, cum_in, cum_out, conv_w and dense_w")
+        _dense_f32(conv_w, "conv_w", (32, 2, 31))
+        _dense_f32(dense_w, "dense_w", (A, 32))
+    else:
+        prev_in = cum_in = cum_out = None
+    ld_in = _same_stride("rnn_attn_step_train", B, Tk, (prev_in, "prev_in"), (cum_in, "cum_in"))
+    ld_out = _same_stride("rnn_attn_step_train", B, Tk, (w_out, "w_out"), (cum_out, "cum_out"))
+    check(lib().unast_rnn_attn_step_train(mode, _p(h), h.stride(0), _p(Wq), _p(mem), _p(v), _p(enc), _p(lens_i32), _p(prev_in), _p(cum_in), ld_in,
+                                          _p(w_out), _p(cum_out), ld_out, _p(conv_w), _p(dense_w), _p(ctx), ldc, B, Tk, A, _stream()),
+          "unast_rnn_attn_step_train")
+    return ctx
+
+
+def rnn_attn_step_bwd_ws(B, Tk, A, device):
+    return torch.empty(lib().unast_rnn_attn_step_bwd_ws_floats(B, Tk, A), dtype=torch.float32, device=device)
+
+
+def rnn_attn_step_bwd(mode, d_ctx, w, h, Wq, mem, v, enc, lens_i32, d_h, d_q, d_mem, dv_part, ws, prev=None, cum=None, conv_w=None, dense_w=None,
+                      d_w_a=None, d_w_b=None, carry=False, ddense_part=None, dconv_part=None, d_prev=None, d_cum=None):
+    """Backward of one attention position (include/unast_hip.h): d_ctx [B,512], the saved weights w (and LSA's prev / cum) [B,Tk] row-strided,
+    the forward's h, Wq, mem, v, enc, lens; incoming weight gradients d_w_a + d_w_b [B,Tk] (None = zero).  Writes d_h [B,256], d_q [B,A]; adds
+    to d_mem [B,Tk,A] and the per-sequence partial sums dv_part [B,A], ddense_part [B,A,32], dconv_part [B,32,2,31]; LSA writes d_prev and
+    d_cum [B,Tk] (d_cum += d_w_b with carry).  ws = rnn_attn_step_bwd_ws(B, Tk, A, device)."""
+    if mode not in (ATTN_LUONG, ATTN_LSA):
+        raise ValueError("rnn_attn_step_bwd: mode must be ATTN_LUONG (0) or ATTN_LSA (1), got %r" % (mode,))
+    B, Tk, A = _attn_operands("rnn_attn_step_bwd", h, Wq, mem, v, enc, lens_i32)
+    lddc = _rows(d_ctx, "d_ctx", B, 512)
+    lddh = _rows(d_h, "d_h", B, 256)
+    lddq = _rows(d_q, "d_q", B, A)
+    _dense_f32(d_mem, "d_mem", (B, Tk, A))
+    _dense_f32(dv_part, "dv_part", (B, A))
+    _dense_f32(ws, "ws")
+    if mode == ATTN_LSA:
+        if any(t is None for t in (prev, cum, conv_w, dense_w, ddense_part, dconv_part, d_prev, d_cum)):
+            raise ValueError("rnn_attn_step_bwd: LSA mode needs prev, cum, conv_w, dense_w, ddense_part, dconv_part, d_prev and d_cum")
+        _dense_f32(conv_w, "conv_w", (32, 2, 31))
+        _dense_f32(dense_w, "dense_w", (A, 32))
+        _dense_f32(ddense_part, "ddense_part", (B, A, 32))
+        _dense_f32(dconv_part, "dconv_part", (B, 32, 2, 31))
+    else:
+        prev = cum = conv_w = dense_w = ddense_part = dconv_part = d_prev = d_cum = None
+    ldw = _same_stride("rnn_attn_step_bwd", B, Tk, (w, "w"), (prev, "prev"), (cum, "cum"))
+    ldd = _same_stride("rnn_attn_step_bwd", B, Tk, (d_w_a, "d_w_a"), (d_w_b, "d_w_b"), (d_prev, "d_prev"), (d_cum, "d_cum"))
+    check(lib().unast_rnn_attn_step_bwd(mode, _p(d_ctx), lddc, _p(w), _p(prev), _p(cum), ldw, _p(h), h.stride(0), _p(Wq), _p(mem), _p(v), _p(enc),
+                                        _p(lens_i32), _p(conv_w), _p(dense_w), _p(d_w_a), _p(d_w_b), int(bool(carry)), ldd, _p(d_h), lddh, _p(d_q), lddq,
+                                        _p(d_mem), _p(dv_part), _p(ddense_part), _p(dconv_part), _p(d_prev), _p(d_cum), _p(ws), ws.numel(), B, Tk, A,
+                                        _stream()), "unast_rnn_attn_step_bwd")
+    return d_h
+
+
+def lstm_cell_train(gates, c_prev, saved, h, mask=None, hd=None):
+    """lstm_cell out of place (h and c_t carry its bits): gates [B,1024], c_prev [B,256]; writes saved [B,5,256] = (i, f, g, o, c_t) and h [B,256];
+    hd [B,256] (optional) = h * mask (mask optional: a dropout factor tensor).  All operands may be row-strided views."""
+    B = gates.shape[0]
+    ldg, ldcp, ldh = _rows(gates, "gates", B, 1024), _rows(c_prev, "c_prev", B, 256), _rows(h, "h", B, 256)
+    _f32(saved, "saved")
+    if saved.dim() != 3 or tuple(saved.shape) != (B, 5, 256) or saved.stride(2) != 1 or saved.stride(1) != 256:
+        raise ValueError("lstm_cell_train: saved must be [B,5,256] with dense rows")
+    if mask is not None and hd is None:
+        raise ValueError("lstm_cell_train: a mask needs hd")
+    ldm = _rows(mask, "mask", B, 256) if mask is not None else 0
+    ldhd = _rows(hd, "hd", B, 256) if hd is not None else 0
+    check(lib().unast_lstm_cell_train(_p(gates), ldg, _p(c_prev), ldcp, _p(saved), saved.stride(0), _p(h), ldh, _p(mask), ldm, _p(hd), ldhd, B, 256,
+                                      _stream()), "unast_lstm_cell_train")
+    return h
+
+
+def lstm_cell_bwd(saved, c_prev, dG, dc_out, dh=None, dh2=None, mask=None, dc_in=None):
+    """Backward of one cell update: dh_total = dh + dh2 * mask (each optional), dc = dc_in + dh_total o (1 - tanh^2 c_t); writes dG [B,1024]
+    (gate pre-activation gradients) and dc_out = dc f (may be dc_in).  Row-strided views are fine."""
+    B = dG.shape[0]
+    ldg, ldcp, lddco = _rows(dG, "dG", B, 1024), _rows(c_prev, "c_prev", B, 256), _rows(dc_out, "dc_out", B, 256)
+    _f32(saved, "saved")
+    if saved.dim() != 3 or tuple(saved.shape) != (B, 5, 256) or saved.stride(2) != 1 or saved.stride(1) != 256:
+        raise ValueError("lstm_cell_bwd: saved must be [B,5,256] with dense rows")
+    if mask is not None and dh2 is None:
+        raise ValueError("lstm_cell_bwd: a mask needs dh2")
+    ld = lambda t, n: _rows(t, n, B, 256) if t is not None else 0                        # noqa: E731
+    check(lib().unast_lstm_cell_bwd(_p(dh), ld(dh, "dh"), _p(dh2), ld(dh2, "dh2"), _p(mask), ld(mask, "mask"), _p(dc_in), ld(dc_in, "dc_in"), _p(saved),
+                                    saved.stride(0), _p(c_prev), ldcp, _p(dG), ldg, _p(dc_out), lddco, B, 256, _stream()), "unast_lstm_cell_bwd")
+    return dG
+
+
+def tanh_bwd(dy2d, y2d):
+    """dy *= 1 - y^2 in place (y = the stored tanh output)."""
+    if not (dy2d.dim() == 2 and dy2d.shape == y2d.shape and dy2d.stride(1) == 1 and y2d.stride(1) == 1):
+        raise ValueError("tanh_bwd: dy and y [rows, C], unit column strides")
+    _f32(dy2d, "dy"), _f32(y2d, "y")
+    check(lib().unast_tanh_bwd(_p(dy2d), dy2d.stride(0), _p(y2d), y2d.stride(0), dy2d.shape[0], dy2d.shape[1], _stream()), "unast_tanh_bwd")
+    return dy2d
+
+
 def tanh_rows(x2d):
     """x = tanh(x) in place over a [rows, cols] view with unit column stride."""
     _f32(x2d, "x")

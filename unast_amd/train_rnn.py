@@ -12,6 +12,13 @@ from the package's counter-based RNG; the tape lists every site (name, p, seed, 
 them (tests/dropout_mirror.py).  Contractions keep fp32-level products in both directions (unast_amd.rnn._linear_rows and its gradient
 forms below).  The recurrence and its backward are unast_lstm_seq_fwd_train / unast_lstm_seq_bwd (csrc/rnn.hip); dW_ih, dW_hh, dx and the
 bias gradients are GEMMs and column sums over the kernel's dxproj.  Everything runs under torch.no_grad() on the current stream.  DESIGN 5i.
+
+SpeechRNN's decoder trains through two more entry points with the same conventions (the second half of this file):
+
+    tape = decoder_forward(model, target, enc_outputs, lens_k, seed=0)      # tape.pre, tape.post [B,T,M], tape.stop [B,T], tape.sites
+    d_enc_output, d_h, d_c = decoder_backward(tape, d_pre, d_post, d_stop)  # writes p.grad of model.prenet, model.decoder, model.postnet
+
+so that the speech autoencoder is encoder_forward -> decoder_forward -> decoder_backward -> encoder_backward(..., accumulate=True).
 """
 import collections
 
@@ -241,11 +248,11 @@ def _prepare_grads(params, accumulate):
         torch._foreach_zero_(gs)
 
 
-def _cot(t, shape, name, dev):
+def _cot(t, shape, name, dev, what="encoder_backward"):
     if t is None:
         return None
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype is _F32 and tuple(t.shape) == tuple(shape)):
-        raise ValueError("encoder_backward: %s must be a float32 CUDA tensor %s" % (name, tuple(shape)))
+        raise ValueError("%s: %s must be a float32 CUDA tensor %s" % (what, name, tuple(shape)))
     return t.detach().contiguous()
 
 
@@ -255,7 +262,7 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
     zero).  Writes p.grad of exactly the parameters under model.prenet and model.encoder, in the reference's shapes: overwritten
     (accumulate=False; an existing dense fp32 .grad is kept in place) or added to (accumulate=True).  Returns d_mel [B,T,num_mels] (speech)
     or None (text).  A tape is used once."""
-    if not isinstance(tape, Tape):
+    if not isinstance(tape, Tape) or isinstance(tape, DecoderTape):
         raise TypeError("encoder_backward: tape must come from encoder_forward")
     if tape.used:
         raise RuntimeError("encoder_backward: this tape has been used; run encoder_forward again")
@@ -340,3 +347,367 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
         ops.rowmask(d_mel, out, NOISE_P, seed, S_NOISE)
         d_mel = out
     return d_mel.view(B, T, M)
+
+
+# ==== SpeechRNN decoder: teacher-forced train-mode decode_sequence (src/network.py:352-377) and its backward; DESIGN 5j ============================
+S_DPRE, S_DDROP, S_DOUT, S_POST = 8, 9, 10, 11      # decoder prenet dropout, nn.LSTM inter-layer, dropout1, the four post-net dropouts (11..14)
+
+class DecoderPack:
+    """The operands the decoder's train kernels read, derived from the parameters of model.prenet, model.decoder and model.postnet: the
+    fp32-level weight pairs of the many-row contractions, and the transposed weights the per-position input-gradient contractions
+    (unast_rnn_linear: Y = X W^T) take as their W."""
+
+    def __init__(self, m):
+        dec, po, pn = m.decoder, m.postnet, m.prenet.layer
+        if dec.num_layers != 2 or dec.attention not in ("luong", "lsa"):
+            raise NotImplementedError("decoder_forward: two decoder layers with 'luong' or 'lsa' attention (what the eval path supports)")
+        self.fcs = [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (pn.fc1, pn.fc2)]
+        r = dec.rnn
+        w0 = r.weight_ih_l0.detach()
+        if tuple(w0.shape) != (1024, 768) or tuple(r.weight_ih_l1.shape) != (1024, 256):
+            raise NotImplementedError("decoder_forward: hidden = e_in = 256 with a 512-wide encoder output")
+        self.w_ih0_p, self.w_ih0_c = _resid(w0[:, :256]), _c(w0[:, 256:])                   # the prenet columns (batched) and the context columns
+        self.w_hh0, self.w_ih1, self.w_hh1 = _c(r.weight_hh_l0), _c(r.weight_ih_l1), _c(r.weight_hh_l1)
+        self.bias = [_c(getattr(r, n)) for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1")]
+        tr = lambda w: w.detach().t().contiguous()                                          # noqa: E731
+        self.wt_ihc0, self.wt_hh0, self.wt_ih1, self.wt_hh1 = tr(w0[:, 256:]), tr(r.weight_hh_l0), tr(r.weight_ih_l1), tr(r.weight_hh_l1)
+        at = dec.attention_layer
+        if dec.attention == "lsa":
+            self.mode = ops.ATTN_LSA
+            self.q_lin, self.mem_lin, self.v_lin = at.query_layer.linear_layer, at.memory_layer.linear_layer, at.v.linear_layer
+            self.conv_mod, self.dense_lin = at.location_layer.location_conv.conv, at.location_layer.location_dense.linear_layer
+            self.conv_w, self.dense_w = _c(self.conv_mod.weight), _c(self.dense_lin.weight)
+        else:
+            self.mode = ops.ATTN_LUONG
+            self.q_lin, self.mem_lin, self.v_lin = at.project_hid, at.project_eo, at.fc2
+            self.conv_mod = self.dense_lin = self.conv_w = self.dense_w = None
+        self.Wq, self.Wmem, self.v = _c(self.q_lin.weight), _resid(self.mem_lin.weight), _c(self.v_lin.weight).view(-1)
+        self.A = self.Wq.shape[0]
+        if self.A % 4 or self.A > 64:
+            raise NotImplementedError("decoder_forward: attn_dim must be a multiple of 4, at most 64 (got %d)" % self.A)
+        self.proj_lin = dec.linear_projection.linear_layer
+        self.proj = (_resid(self.proj_lin.weight), _c(self.proj_lin.bias))
+        M = po.linear_project.weight.shape[0]
+        self.M, self.ldh = M, (M + 1 + 3) // 4 * 4                                          # [linear_project | stop_linear | zero rows] as one head
+        Wh = torch.zeros(self.ldh, 256, dtype=_F32, device=w0.device)
+        bh = torch.zeros(self.ldh, dtype=_F32, device=w0.device)
+        Wh[:M].copy_(po.linear_project.weight.detach())
+        Wh[M].copy_(po.stop_linear.weight.detach()[0])
+        bh[:M].copy_(po.linear_project.bias.detach())
+        bh[M:M + 1].copy_(po.stop_linear.bias.detach())
+        self.head = (_resid(Wh), bh)
+        stages = [(po.conv1.conv, po.pre_batchnorm)] + [(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
+        self.post = [(_resid(conv.weight.detach().permute(0, 2, 1)), _c(conv.bias), conv, bn) for conv, bn in stages]
+        self.post_out = (_resid(po.conv2.conv.weight.detach().permute(0, 2, 1)), _c(po.conv2.conv.bias), po.conv2.conv)
+
+
+def _decoder_params(model):
+    return list(model.prenet.parameters()) + list(model.decoder.parameters()) + list(model.postnet.parameters())
+
+
+def decoder_pack_of(m):
+    ver, dev = 0, None
+    for t in _decoder_params(m):
+        ver += t._version
+        dev = t.device
+    key = (ver, dev)
+    cached = m.__dict__.get("_rnn_decoder_train_pack")
+    if cached is None or cached[0] != key:
+        cached = (key, DecoderPack(m))
+        m.__dict__["_rnn_decoder_train_pack"] = cached
+    return cached[1]
+
+
+class DecoderTape(Tape):
+    """What decoder_forward returns and decoder_backward consumes (once): .pre, .post [B,T,M], .stop [B,T], .sites."""
+
+    def saved_bytes(self):
+        """Bytes of the state kept for the backward (the slabs of the forward loop and of the batched stages)."""
+        seen, n = set(), 0
+        for v in self.__dict__.values():
+            for t in (v if isinstance(v, (list, tuple)) else [v]):
+                if torch.is_tensor(t) and t.is_cuda and t.untyped_storage().data_ptr() not in seen:
+                    seen.add(t.untyped_storage().data_ptr())
+                    n += t.untyped_storage().nbytes()
+        return n
+
+
+def _drop_factor(p, seed, stream, rows, cols, dev):
+    """The factor tensor of a dropout site [rows, cols] (0 or 1/(1-p)): the element-wise kernel's mask applied to ones."""
+    ones = torch.ones(rows, cols, dtype=_F32, device=dev)
+    f = torch.empty_like(ones)
+    ops.leaky_dropout(ones, None, f, 1.0, p, seed, stream)
+    return f
+
+
+@torch.no_grad()
+def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
+    """Train-mode, teacher-forced SpeechRNN.decode_sequence (teacher_ratio = 1): target [B,T,num_mels] on the GPU, enc_outputs = ((h, c)
+    [2,B,256], enc_output [B,Tk,512]) or an encoder Tape, lens_k the live keys per sequence (1..Tk).  Returns a DecoderTape: .pre and .post
+    [B,T,num_mels], .stop [B,T].  Updates the post-net's BatchNorm running statistics and drops the model's cached eval operands.
+    mark (optional): called with 'loop_begin' / 'loop_end' around the position loop (a caller that times it records an event there)."""
+    from .network import TextRNN, SpeechRNN
+    if isinstance(model, TextRNN):
+        raise NotImplementedError("decoder_forward: SpeechRNN only -- TextRNN.decode runs TextPrenet over the whole prefix at every position "
+                                  "(batch-statistics BatchNorm over B*(i+1) rows and a running-statistics update per position, O(T^2))")
+    if not isinstance(model, SpeechRNN):
+        raise TypeError("decoder_forward: model must be a unast_amd.network.SpeechRNN")
+    if not model.training:
+        raise RuntimeError("decoder_forward is the train-mode entry point: call model.train() first (model.decode_sequence() is the eval forward)")
+    if isinstance(enc_outputs, Tape):
+        enc_outputs = (enc_outputs.hidden, enc_outputs.enc_output)
+    mel = model._mel(target)
+    (h0, c0), enc = enc_outputs
+    B, T, M = mel.shape
+    if T < 1 or not (torch.is_tensor(enc) and enc.is_cuda and enc.dim() == 3 and enc.shape[0] == B and enc.shape[2] == 512):
+        raise ValueError("decoder_forward: enc_output must be a CUDA tensor [B,Tk,512] with target's B, T >= 1")
+    Tk = enc.shape[1]
+    if not 1 <= Tk <= 2048:
+        raise ValueError("decoder_forward: 1 <= Tk <= 2048 (got %d)" % Tk)
+    for t, n in ((h0, "h"), (c0, "c")):
+        if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == (2, B, 256)):
+            raise ValueError("decoder_forward: %s must be a CUDA tensor [2,B,256]" % n)
+    lens_l = [int(v) for v in (lens_k.tolist() if hasattr(lens_k, "tolist") else lens_k)]
+    if len(lens_l) != B or min(lens_l) < 1 or max(lens_l) > Tk:
+        raise ValueError("decoder_forward: lens_k must hold one length in 1..Tk = %d per sequence (got %r)" % (Tk, lens_l))
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError("unast_amd runs on the GPU only: move the model to a CUDA (ROCm) device first; there is no CPU path")
+    dev = mel.device
+    P = decoder_pack_of(model)
+    enc, h0, c0 = (t.detach().to(_F32).contiguous() for t in (enc, h0, c0))
+    lens = torch.tensor(lens_l, dtype=torch.int32, device=dev)
+    tape = DecoderTape()
+    tape.model, tape.P, tape.lens, tape.B, tape.T, tape.Tk = model, P, lens, B, T, Tk
+    tape.seed, tape.epoch = int(seed), ops.rng_epoch_counter().clone()
+    tape.enc, tape.h0, tape.c0 = enc, h0, c0
+    N, A, lsa = B * T, P.A, P.mode == ops.ATTN_LSA
+    p_pre, p_dec, p_post = float(model.prenet.p), float(model.decoder.p), float(model.postnet.p)
+
+    # ---- batched before the loop: the prenet on all fed frames, W_ih_l0[:, :256] P + b_ih, the memory-side projection ----------------------
+    feed = ops.shift_frames(mel, torch.empty_like(mel)).view(N, M)                          # feed_0 = 0, feed_i = target[:, i-1]
+    (w1, b1, _), (w2, b2, _) = P.fcs
+    a1 = _linear_rows(feed, w1, b1)
+    h1 = torch.empty_like(a1)
+    ops.leaky_dropout(a1, None, h1, 0.0, p_pre, seed, S_DPRE)
+    tape.site("d_prenet_dropout", p_pre, S_DPRE, N, a1.shape[1])
+    pre = _linear_rows(h1, w2, b2, act=1)
+    xp0 = _linear_rows(pre, P.w_ih0_p, P.bias[0]).view(B, T, 1024)
+    mem = _linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, A)
+    tape.feed, tape.a1, tape.h1, tape.pre_act, tape.mem = feed, a1, h1, pre, mem
+
+    # ---- the loop: per position 7 launches on host-indexed slices of [B,T,...] slabs -------------------------------------------------------------
+    Tkp = (Tk + 3) // 4 * 4
+    W = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev)                                  # W[:, i+1] = w_i; W[:, 0] = 0 is position 0's prev
+    CUM = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev) if lsa else None               # CUM[:, i] = what position i read
+    HC = _buf(B, T, 768, dev=dev)                                                           # [h1_i | ctx_i]: the projection's input rows
+    H0 = _buf(B, T + 1, 256, dev=dev)                                                       # H0[:, i] = layer 0's h before position i
+    H0[:, 0].copy_(h0[0])
+    S0, S1 = _buf(B, T, 5, 256, dev=dev), _buf(B, T, 5, 256, dev=dev)
+    F1 = _drop_factor(p_dec, seed, S_DDROP, N, 256, dev).view(B, T, 256) if p_dec > 0.0 else None
+    tape.site("d_drop0", p_dec, S_DDROP, N, 256)
+    H0d = _buf(B, T, 256, dev=dev) if F1 is not None else None
+    ga, gb = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev)
+    b_ih0, b_hh0, b_ih1, b_hh1 = P.bias
+    if mark is not None:
+        mark("loop_begin")
+    for i in range(T):
+        q = HC[:, i - 1, :256] if i else h0[1]                                             # the top layer's h from BEFORE this position's LSTM
+        ops.rnn_attn_step_train(P.mode, q, P.Wq, mem, P.v, enc, lens, HC[:, i, 256:], W[:, i + 1, :Tk], prev_in=W[:, i, :Tk],
+                                cum_in=CUM[:, i, :Tk] if lsa else None, cum_out=CUM[:, i + 1, :Tk] if lsa else None, conv_w=P.conv_w, dense_w=P.dense_w)
+        ops.rnn_linear(HC[:, i, 256:], P.w_ih0_c, None, gb, R=xp0[:, i])
+        ops.rnn_linear(H0[:, i], P.w_hh0, b_hh0, ga, R=gb)
+        ops.lstm_cell_train(ga, S0[:, i - 1, 4] if i else c0[0], S0[:, i], H0[:, i + 1], mask=F1[:, i] if F1 is not None else None,
+                            hd=H0d[:, i] if F1 is not None else None)
+        ops.rnn_linear(H0d[:, i] if F1 is not None else H0[:, i + 1], P.w_ih1, b_ih1, gb)
+        ops.rnn_linear(q, P.w_hh1, b_hh1, ga, R=gb)
+        ops.lstm_cell_train(ga, S1[:, i - 1, 4] if i else c0[1], S1[:, i], HC[:, i, :256])
+    if mark is not None:
+        mark("loop_end")
+    tape.W, tape.CUM, tape.HC, tape.H0, tape.H0d, tape.S0, tape.S1, tape.F1 = W, CUM, HC, H0, H0d, S0, S1, F1
+
+    # ---- batched after the loop: projection + tanh + dropout1, the head, the post-net ------------------------------------------------------------
+    tz = ops.tanh_rows(_linear_rows(HC.view(N, 768), P.proj[0], P.proj[1]))
+    o = tz
+    if p_dec > 0.0:
+        o = torch.empty_like(tz)
+        ops.leaky_dropout(tz, None, o, 1.0, p_dec, seed, S_DOUT)
+    tape.site("d_dropout1", p_dec, S_DOUT, N, 256)
+    head = _linear_rows(o, P.head[0], P.head[1]).view(B, T, P.ldh)
+    outs = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)                                 # position 0 = the all-zero go frame
+    outs[:, 1:].copy_(head[:, :, :M])
+    tape.tz, tape.o, tape.stop = tz, o, head[:, :, M].contiguous()
+    N1 = B * (T + 1)
+    tape.xs, tape.zs = [outs.view(N1, M)], []
+    tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
+    bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
+    cur = outs
+    for k, (wp, bias, _, bn) in enumerate(P.post):
+        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+            raise NotImplementedError("decoder_forward: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)")
+        z = _conv(cur, wp, bias, 4).view(N1, 256)
+        y = _buf(N1, 256, dev=dev)
+        ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, 2, drop_p=p_post, seed=seed,
+                   stream_id=S_POST + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
+        tape.site("post_dropout%d" % k, p_post, S_POST + k, N1, 256)
+        tape.zs.append(z)
+        tape.xs.append(y)
+        cur = y.view(B, T + 1, 256)
+    post = _conv(cur, P.post_out[0], P.post_out[1], 4)
+    ops.add_inplace(post, outs)
+    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    tape.pre, tape.post = outs[:, 1:], post[:, 1:]
+    return tape
+
+
+def _conv_grads(dz2d, x2d, B, T, wpair, conv, pad_left):
+    """Weight, bias and input gradient of one tap-major conv with fp32-level products (the text prenet's form in encoder_backward)."""
+    wp, wr = wpair
+    C, Cin = dz2d.shape[1], x2d.shape[1]
+    dz, dzh, dzr = (t.view(B, T, C) for t in _parts(dz2d))
+    gw = torch.zeros_like(wp)
+    x3, x3res = x2d.view(B, T, Cin), _resid_of(x2d).view(B, T, Cin)
+    ops.conv_taps_wgrad(dzh, x3, gw, pad_left)
+    ops.conv_taps_wgrad(dzr, x3, gw, pad_left)
+    ops.conv_taps_wgrad(dz, x3res, gw, pad_left)
+    conv.weight.grad.add_(gw.permute(0, 2, 1))
+    ops.colsum(dz.view(B * T, C), conv.bias.grad)
+    dx = _buf(B, T, Cin, dev=dz2d.device)
+    ops.conv_taps_dgrad(dzh, wp, dx, pad_left)
+    ops.conv_taps_dgrad(dzr, wp, dx, pad_left, beta=1)
+    ops.conv_taps_dgrad(dz, wr, dx, pad_left, beta=1)
+    return dx.view(B * T, Cin)
+
+
+def _add_over_b(part, grad):
+    """grad += sum_b part[b] in the fixed order b = 0, 1, ... (the per-sequence partial sums of unast_rnn_attn_step_bwd)."""
+    flat = grad.view(-1)
+    for b in range(part.shape[0]):
+        ops.add_inplace(flat, part[b])
+
+
+@torch.no_grad()
+def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=False, mark=None):
+    """Backward of decoder_forward for the scalar whose gradients with respect to pre, post [B,T,num_mels] and stop [B,T] are given (None =
+    zero).  Writes p.grad of exactly the parameters under model.prenet, model.decoder and model.postnet (overwritten, or added to with
+    accumulate=True; an existing dense fp32 .grad is kept in place).  Returns (d_enc_output [B,Tk,512], d_h, d_c [2,B,256]), the cotangents
+    encoder_backward takes.  A tape is used once.  mark: as decoder_forward's."""
+    if not isinstance(tape, DecoderTape):
+        raise TypeError("decoder_backward: tape must come from decoder_forward")
+    if tape.used:
+        raise RuntimeError("decoder_backward: this tape has been used; run decoder_forward again")
+    model, P, B, T, Tk, seed, lens = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens
+    M, A, ldh, lsa = P.M, P.A, P.ldh, P.mode == ops.ATTN_LSA
+    N, N1 = B * T, B * (T + 1)
+    dev = tape.enc.device
+    d_pre, d_post = _cot(d_pre, (B, T, M), "d_pre", dev, "decoder_backward"), _cot(d_post, (B, T, M), "d_post", dev, "decoder_backward")
+    d_stop = _cot(d_stop, (B, T), "d_stop", dev, "decoder_backward")
+    tape.used = True
+    _prepare_grads(_decoder_params(model), accumulate)
+    po, dec = model.postnet, model.decoder
+    p_pre, p_dec, p_post = float(model.prenet.p), float(dec.p), float(po.p)
+
+    # ---- batched before the loop: the post-net into d_outputs, the head, dropout1, tanh, the projection -----------------------------------------
+    d_head = torch.zeros(B, T, ldh, dtype=_F32, device=dev)
+    if d_post is not None:
+        dpf = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)
+        dpf[:, 1:].copy_(d_post)
+        dy = _conv_grads(dpf.view(N1, M), tape.xs[4], B, T + 1, P.post_out[0], P.post_out[2], 4)
+        bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
+        for k in (3, 2, 1, 0):
+            wpair, _, conv, bn = P.post[k]
+            dz = _buf(N1, 256, dev=dev)
+            ops.bn_bwd(dy, tape.zs[k], tape.mean[k], tape.rstd[k], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 2, drop_p=p_post, seed=seed,
+                       stream_id=S_POST + k)
+            dy = _conv_grads(dz, tape.xs[k], B, T + 1, wpair, conv, 4)
+        ops.add_inplace(dpf, dy)                                                            # outputs + postnet(outputs): the residual's share
+        d_head[:, :, :M].copy_(dpf[:, 1:])                                                  # (the go frame's gradient is dropped: a constant)
+    if d_pre is not None:
+        d_head[:, :, :M].add_(d_pre)
+    if d_stop is not None:
+        d_head[:, :, M].copy_(d_stop)
+    dhp = _parts(d_head.view(N, ldh))
+    gW, gb = torch.zeros(ldh, 256, dtype=_F32, device=dev), torch.zeros(ldh, dtype=_F32, device=dev)
+    _wgrad_rows(dhp, ALL, tape.o, _resid_of(tape.o), gW, (gb,))
+    po.linear_project.weight.grad.add_(gW[:M])
+    po.linear_project.bias.grad.add_(gb[:M])
+    po.stop_linear.weight.grad.add_(gW[M:M + 1])
+    po.stop_linear.bias.grad.add_(gb[M:M + 1])
+    d_o = _dgrad_rows(dhp, P.head[0], _buf(N, 256, dev=dev))
+    if p_dec > 0.0:
+        d_od = torch.empty_like(d_o)
+        ops.leaky_dropout(d_o, d_o, d_od, 1.0, p_dec, seed, S_DOUT)                         # slope 1: the mask and its 1/(1-p) only
+        d_o = d_od
+    dzp = _parts(ops.tanh_bwd(d_o, tape.tz))
+    HC2 = tape.HC.view(N, 768)
+    HC2res = _resid_of(HC2)
+    _wgrad_rows(dzp, ALL, HC2, HC2res, P.proj_lin.weight.grad, (P.proj_lin.bias.grad,))
+    DHC = _dgrad_rows(dzp, P.proj[0], _buf(N, 768, dev=dev)).view(B, T, 768)                # [d_h1 | d_ctx] of the projection, all positions
+
+    # ---- the loop, i = T-1 .. 0: 7 launches per position --------------------------------------------------------------------------------------------
+    z = lambda *s: torch.zeros(*s, dtype=_F32, device=dev)                                  # noqa: E731
+    Tkp = tape.W.shape[2]
+    dh0, dh1, dc0, dc1 = z(B, 256), z(B, 256), z(B, 256), z(B, 256)
+    DG0, DG1 = _buf(B, T, 1024, dev=dev), _buf(B, T, 1024, dev=dev)
+    DCTX, DQ = _buf(B, T, 512, dev=dev), _buf(B, T, A, dev=dev)
+    d_mem, dv_part = z(B, Tk, A), z(B, A)
+    dd_part, dcv_part = (z(B, A, 32), z(B, 32, 2, 31)) if lsa else (None, None)
+    dprev, dcum = ([z(B, Tkp), z(B, Tkp)], [z(B, Tkp), z(B, Tkp)]) if lsa else ([None, None], [None, None])
+    ws = ops.rnn_attn_step_bwd_ws(B, Tk, A, dev)
+    t256, dh_att = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+    W, CUM, HC, S0, S1, F1, h0, c0 = tape.W, tape.CUM, tape.HC, tape.S0, tape.S1, tape.F1, tape.h0, tape.c0
+    sl = lambda t: t[:, :Tk] if t is not None else None                                     # noqa: E731
+    if mark is not None:
+        mark("loop_begin")
+    for i in range(T - 1, -1, -1):
+        cur, nxt = (T - 1 - i) & 1, (T - i) & 1
+        ops.lstm_cell_bwd(S1[:, i], S1[:, i - 1, 4] if i else c0[1], DG1[:, i], dc1, dh=dh1, dh2=DHC[:, i, :256], dc_in=dc1)
+        ops.rnn_linear(DG1[:, i], P.wt_ih1, None, t256)                                     # dG1 W_ih_l1: layer 0's output gradient, masked below
+        ops.lstm_cell_bwd(S0[:, i], S0[:, i - 1, 4] if i else c0[0], DG0[:, i], dc0, dh=dh0, dh2=t256, mask=F1[:, i] if F1 is not None else None, dc_in=dc0)
+        ops.rnn_linear(DG0[:, i], P.wt_ihc0, None, DCTX[:, i], R=DHC[:, i, 256:])           # d_ctx = the projection's share + dG0 W_ih_l0[:, 256:]
+        q = HC[:, i - 1, :256] if i else h0[1]
+        ops.rnn_attn_step_bwd(P.mode, DCTX[:, i], W[:, i + 1, :Tk], q, P.Wq, tape.mem, P.v, tape.enc, lens, dh_att, DQ[:, i], d_mem, dv_part, ws,
+                              prev=W[:, i, :Tk], cum=CUM[:, i, :Tk] if lsa else None, conv_w=P.conv_w, dense_w=P.dense_w, d_w_a=sl(dprev[cur]),
+                              d_w_b=sl(dcum[cur]), carry=True, ddense_part=dd_part, dconv_part=dcv_part, d_prev=sl(dprev[nxt]), d_cum=sl(dcum[nxt]))
+        ops.rnn_linear(DG1[:, i], P.wt_hh1, None, dh1, R=dh_att)                            # the query was h1_{i-1}: its gradient joins layer 1's carry
+        ops.rnn_linear(DG0[:, i], P.wt_hh0, None, dh0)
+    if mark is not None:
+        mark("loop_end")
+
+    # ---- batched after the loop: every weight and bias gradient, the prenet, the memory side ---------------------------------------------------------
+    r = dec.rnn
+    dg0p, dg1p = _parts(DG0.view(N, 1024)), _parts(DG1.view(N, 1024))
+    pre = tape.pre_act
+    _wgrad_rows(dg0p, ALL, pre, _resid_of(pre), r.weight_ih_l0.grad[:, :256], (r.bias_ih_l0.grad, r.bias_hh_l0.grad))
+    _wgrad_rows(dg0p, ALL, HC2[:, 256:], HC2res[:, 256:], r.weight_ih_l0.grad[:, 256:])
+    h0prev = tape.H0[:, :T].contiguous().view(N, 256)
+    _wgrad_rows(dg0p, ALL, h0prev, _resid_of(h0prev), r.weight_hh_l0.grad)
+    x1 = (tape.H0d if F1 is not None else tape.H0[:, 1:].contiguous()).view(N, 256)
+    _wgrad_rows(dg1p, ALL, x1, _resid_of(x1), r.weight_ih_l1.grad, (r.bias_ih_l1.grad, r.bias_hh_l1.grad))
+    qry = torch.cat([h0[1][:, None, :], HC[:, :T - 1, :256]], 1).contiguous().view(N, 256)  # h1 before each position: W_hh_l1's input and the queries
+    qry_res = _resid_of(qry)
+    _wgrad_rows(dg1p, ALL, qry, qry_res, r.weight_hh_l1.grad)
+    _wgrad_rows(_parts(DQ.view(N, A)), ALL, qry, qry_res, P.q_lin.weight.grad)
+    _add_over_b(dv_part, P.v_lin.weight.grad)
+    if lsa:
+        _add_over_b(dd_part, P.dense_lin.weight.grad)
+        _add_over_b(dcv_part, P.conv_mod.weight.grad)
+    # the prenet (shared with the encoder)
+    d_p = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev))
+    (w1, _, fc1), (w2, _, fc2) = P.fcs
+    ops.relu_bwd(d_p, pre)
+    dpp = _parts(d_p)
+    _wgrad_rows(dpp, ALL, tape.h1, _resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
+    dh1p = _dgrad_rows(dpp, w2, _buf(N, tape.h1.shape[1], dev=dev))
+    da1 = torch.empty_like(dh1p)
+    ops.leaky_dropout(tape.a1, dh1p, da1, 0.0, p_pre, seed, S_DPRE)
+    _wgrad_rows(_parts(da1), ALL, tape.feed, _resid_of(tape.feed), fc1.weight.grad, (fc1.bias.grad,))
+    # the memory side: dW_mem = d_mem^T enc, d_enc = d_mem W_mem + per sequence w_b^T [Tk,T] . d_ctx_b [T,512] (formed once, after the loop)
+    enc2 = tape.enc.view(B * Tk, 512)
+    dmp = _parts(d_mem.view(B * Tk, A))
+    _wgrad_rows(dmp, ALL, enc2, _resid_of(enc2), P.mem_lin.weight.grad)
+    d_enc = _dgrad_rows(dmp, P.Wmem, _buf(B * Tk, 512, dev=dev)).view(B, Tk, 512)
+    wparts = _parts(W[:, 1:])
+    dctx_res = _resid_of(DCTX)
+    for b in range(B):
+        _wgrad_rows(tuple(t[b] for t in wparts), slice(0, Tk), DCTX[b], dctx_res[b], d_enc[b])
+    return d_enc, torch.stack([dh0, dh1]), torch.stack([dc0, dc1])

@@ -351,6 +351,33 @@ int unast_lstm_cell_bwd(const float* dh, int lddh, const float* dh2, int lddh2, 
 int unast_tanh_bwd(float* dy, int lddy, const float* y, int ldy, int rows, int cols, hipStream_t stream);
 /* x = tanh(x) over [rows, cols]: the tanh behind RNNDecoder's linear_projection (src/module.py:373). */
 int unast_tanh_rows(float* x, int ldx, int rows, int cols, hipStream_t stream);
+/* The prefix prenet of TextRNN's teacher-forced decoder training (csrc/prefix.hip): TextPrenet over every prefix at once.  The slab
+ * (unast_amd.train_rnn.prefix_layout): segment s = 0..T-1 holds B sequences of L_s = max(s,1) live rows, each followed by two gap rows;
+ * segoff int32 [T+1] = first row of each segment (segoff[T] = slab_rows); chunks int32 [nchunks,2] = {segment, first row} of runs of at most 64
+ * rows inside one segment, in slab order; chunk_start int32 [T+1] = first chunk of each segment.  2 <= B, 1 <= T <= 512, slab_rows*C*4 < 2 GiB.
+ * No atomics; sums in a fixed order (fp64).
+ * unast_prefix_bn_fwd: train-mode BatchNorm + ReLU + dropout with statistics per segment over its B*L_s live rows (gap rows of x are not
+ *   read); y [slab_rows,C] gets exact zeros on gap rows, or (stage 3) p_last [B,T,C] gets each prefix's last row; exactly one of the two.
+ *   mean, rstd, varu (unbiased variance) [T,C]; the running statistics take T momentum updates in segment order, num_batches_tracked += T.
+ *   ws: nchunks*2*C doubles.  The dropout mask's row index is the slab row.
+ * unast_prefix_bn_bwd: dz [slab_rows,C] = rstd gamma (g - mean_s(g) - xhat mean_s(g xhat)), g = dy gated by the recomputed ReLU and mask; zeros on
+ *   gap rows; dgamma, dbeta += sums over segments in order.  last_only: dy is d_P [B,T,C] (each prefix's last row), else [slab_rows,C] whose gap
+ *   rows are not read.  ws: (nchunks + T)*2*C doubles.
+ * unast_prefix_embed_fwd: out[row(s,b,j)] = dropout(E[id]), id = sos at s = 0 and target[b,j] (int64 [B,T]) after that; zeros on gap rows.
+ * unast_prefix_embed_bwd: G [B,T+1,C]: G[b,0] = the masked gradient of segment 0's row, G[b,1+t] = sum over s > t of the masked gradient rows of
+ *   target[b,t], segments in order; unast_embed_bwd over the ids [sos | target] scatters G into dE. */
+int unast_prefix_bn_fwd(const float* x, const int* chunks, const int* chunk_start, const int* segoff, int nchunks, int slab_rows, int B, int T, int C,
+                        const float* gamma, const float* beta, float* y, float* p_last, float* mean, float* rstd, float* varu,
+                        float* running_mean, float* running_var, int64_t* num_batches_tracked, double* ws, float eps,
+                        float momentum, float drop_p, unsigned int seed, unsigned int stream_id, hipStream_t stream);
+int unast_prefix_bn_bwd(const float* dy, int last_only, const float* x, const int* chunks, const int* chunk_start, const int* segoff, int nchunks,
+                        int slab_rows, int B, int T, int C, const float* mean, const float* rstd, const float* gamma, const float* beta, float* dz,
+                        float* dgamma, float* dbeta, double* ws, float drop_p, unsigned int seed, unsigned int stream_id,
+                        hipStream_t stream);
+int unast_prefix_embed_fwd(const int64_t* target, const float* E, const int* chunks, const int* segoff, int nchunks, int slab_rows, int B, int T, int C,
+                           int vocab, int sos, float* out, float drop_p, unsigned int seed, unsigned int stream_id, hipStream_t stream);
+int unast_prefix_embed_bwd(const float* dx, const int* segoff, int slab_rows, int B, int T, int C, float* G, float drop_p, unsigned int seed,
+                           unsigned int stream_id, hipStream_t stream);
 /* TextRNN.decode's prenet input (src/network.py:573 runs TextPrenet over the whole prefix and keeps its last position, which depends on the
  * prefix's last 7 tokens): out [B,W,E] = embedding rows of prefix positions p-W+1 .. p, zero rows for positions before the prefix.  The prefix at
  * device position *pos is tokens[b, 0..*pos] (generation, src/network.py:590-600; p = *pos) or, teacher_forced, [sos] at *pos = 0 and

@@ -7,7 +7,10 @@ unast_lstm_seq_bwd per recurrent step, and train_rnn.encoder_forward + encoder_b
 --train-decoder: SpeechRNN decoder training at B = 32, T = 800, Tk in {180, 800}, both attention types (dropout on) -- decoder_forward,
 decoder_forward + decoder_backward, the per-position time of each loop (events recorded through the entry points' `mark` callback), the eval
 teacher-forced position of the same session as the yardstick, unast_rnn_attn_step_bwd next to unast_rnn_attn_step, and the saved-state bytes.
-Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder]"""
+--train-text-decoder: TextRNN decoder training at T = 180, B in {4, 16, 32}, Tk in {180, 800}, both attention types (dropout on) --
+text_decoder_forward, forward + backward, the prefix prenet's share, the loops' per-position times next to SpeechRNN's at the same shapes, the
+saved bytes, and the prefix prenet issued position by position through the uniform-[B,T] entry points as the comparator of the slab form.
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder]"""
 import argparse
 import os
 import statistics
@@ -27,6 +30,7 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--frames", type=int, default=800)
 ap.add_argument("--train", action="store_true")
 ap.add_argument("--train-decoder", action="store_true")
+ap.add_argument("--train-text-decoder", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -153,8 +157,113 @@ def train_decoder_mode():
                   % (attn, Tk, f_eval * 1e3, clone * 1e3, f_train * 1e3, bw * 1e3))
 
 
+def prefix_position_loop(P, ids, p, seed, params):
+    """The comparator of --train-text-decoder: the prefix prenet's forward and backward issued position by position through the uniform-[B,T]
+    entry points (unast_embed_fwd / _bwd, _conv, unast_bn_fwd / _bwd, the conv gradients) -- the same arithmetic as the slab form, about
+    100 launches of a few hundred rows per position.  Timing only: the gradients land in the model's .grad."""
+    from unast_amd import train_rnn as TR
+    from unast_amd.utils import SOS_IDX
+    Bb, T = ids.shape
+    E = P.emb.shape[1]
+    TR._prepare_grads(params, False)
+    sos = torch.full((Bb, 1), SOS_IDX, dtype=torch.int64, device=D)
+    bn_ws = torch.empty(512, dtype=torch.float64, device=D)
+    saved = []
+    for s in range(T):
+        tok = (sos if s == 0 else ids[:, :s]).contiguous()
+        L = tok.shape[1]
+        N = Bb * L
+        x0 = torch.empty(N, E, device=D)
+        ops.embed_fwd(tok, P.emb, x0, L, drop_p=p, seed=seed, stream_id=40)
+        xs, zs, mean, rstd = [x0], [], torch.empty(3, 256, device=D), torch.empty(3, 256, device=D)
+        cur = x0.view(Bb, L, E)
+        for i, (wp, bias, _, bn) in enumerate(P.convs):
+            z = TR._conv(cur, wp, bias, 2).view(N, 256)
+            y = torch.empty(N, 256, device=D)
+            ops.bn_fwd(z, bn.weight, bn.bias, y, mean[i], rstd[i], bn.running_mean, bn.running_var, bn_ws, 1, drop_p=p, seed=seed, stream_id=41 + i, eps=bn.eps,
+                       momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
+            zs.append(z)
+            xs.append(y)
+            cur = y.view(Bb, L, 256)
+        saved.append((tok, xs, zs, mean, rstd))
+    for s in range(T - 1, -1, -1):
+        tok, xs, zs, mean, rstd = saved[s]
+        L = tok.shape[1]
+        N = Bb * L
+        dy = torch.zeros(Bb, L, 256, device=D)
+        dy[:, -1] = 1.0                                                                           # d_P: on the prefix's last row only
+        dy = dy.view(N, 256)
+        for i in (2, 1, 0):
+            wpair, _, conv, bn = P.convs[i]
+            dz = torch.empty(N, 256, device=D)
+            ops.bn_bwd(dy, zs[i], mean[i], rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 1, drop_p=p, seed=seed, stream_id=41 + i)
+            dy = TR._conv_grads(dz, xs[i], Bb, L, wpair, conv, 2)
+        ops.embed_bwd(tok, dy, P.emb_grad, L, drop_p=p, seed=seed, stream_id=40, padding_idx=0)
+
+
+def train_text_decoder_mode():
+    """TextRNN decoder training at T = 180 (B in {4, 16, 32}; the RNN configs train at 4 and 16), Tk in {180, 800}, both attention types, dropout
+    on: text_decoder_forward, forward + backward, the prefix prenet's share of each, the per-position loop times next to SpeechRNN's at the same
+    B / T / Tk in the same session, the saved bytes -- and, once per B (it does not depend on the attention or Tk), the prefix prenet's forward +
+    backward in the slab form against the position-by-position comparator."""
+    from unast_amd import train_rnn
+    g = torch.Generator().manual_seed(0)
+    T = TT
+    for Bb in (4, 16, 32):
+        text, mel, _, _ = (torch.from_numpy(x) for x in synth_batch(Bb, T, T, seed=3))
+        text, mel = text.to(D), mel[:, :T].contiguous().to(D)
+        for attn in ("luong", "lsa"):
+            tm, sm = models(attn)
+            tm.train(), sm.train()
+            for Tk in (TT, TM):
+                enc = torch.randn(Bb, Tk, 512, generator=g).to(D) * 0.5
+                hc = (torch.randn(2, Bb, 256, generator=g).to(D) * 0.5, torch.randn(2, Bb, 256, generator=g).to(D) * 0.5)
+                lens_k = [Tk] * Bb
+                cot = torch.randn(Bb, T, 46, device=D)
+                scot = (torch.randn(Bb, T, mel.shape[2], device=D), torch.randn(Bb, T, mel.shape[2], device=D), torch.randn(Bb, T, device=D))
+                keep = []
+                fw = median_ms(lambda: keep.__setitem__(slice(None), [train_rnn.text_decoder_forward(tm, text, (hc, enc), lens_k, seed=3)]))
+                saved = keep[0].saved_bytes()
+                del keep[:]
+                ev = {}
+
+                def marker(side):
+                    def mark(name):
+                        e = torch.cuda.Event(enable_timing=True)
+                        e.record()
+                        ev.setdefault((side, name), []).append(e)
+                    return mark
+
+                def span(side, what):
+                    b, e = ev[(side, what + "_begin")], ev[(side, what + "_end")]
+                    return statistics.median(x.elapsed_time(y) for x, y in zip(b, e))
+                fb = median_ms(lambda: train_rnn.text_decoder_backward(train_rnn.text_decoder_forward(tm, text, (hc, enc), lens_k, seed=3, mark=marker("tf")), cot,
+                                                                       mark=marker("tb")))
+                sfb = median_ms(lambda: train_rnn.decoder_backward(train_rnn.decoder_forward(sm, mel, (hc, enc), lens_k, seed=3, mark=marker("sf")), *scot,
+                                                                   mark=marker("sb")))
+                pf, pb = span("tf", "prefix"), span("tb", "prefix")
+                print("[%s] B=%d T=%d Tk=%d dropout on: text_decoder_forward %.1f ms, forward + backward %.1f ms; prefix prenet %.1f ms forward + %.1f ms backward "
+                      "(%.0f %% of forward + backward); per position: forward loop %.1f us (speech %.1f), backward loop %.1f us (speech %.1f); speech forward + "
+                      "backward %.1f ms; saved state %.1f MiB"
+                      % (attn, Bb, T, Tk, fw, fb, pf, pb, 100 * (pf + pb) / fb, span("tf", "loop") * 1e3 / T, span("sf", "loop") * 1e3 / T,
+                         span("tb", "loop") * 1e3 / T, span("sb", "loop") * 1e3 / T, sfb, saved / 2 ** 20))
+            if attn == "luong":
+                P = train_rnn.decoder_pack_of(tm, train_rnn.TextDecoderPack)
+                params = list(tm.prenet.parameters())
+                train_rnn._prepare_grads(params, False)
+                P.emb_grad = tm.prenet.embed.weight.grad
+                p = float(tm.prenet.p)
+                loop = median_ms(lambda: prefix_position_loop(P, text, p, 3, params), reps=3)
+                lay = train_rnn.prefix_layout(Bb, T)
+                print("prefix prenet B=%d T=%d (%d slab rows, %d live): slab form %.1f ms forward + backward (the figures above), position-by-position "
+                      "comparator %.1f ms" % (Bb, T, lay.total, lay.total - 2 * Bb * T, pf + pb, loop))
+
+
 if a.train:
     train_mode()
+    sys.exit(0)
+if a.train_text_decoder:
+    train_text_decoder_mode()
     sys.exit(0)
 if a.train_decoder:
     train_decoder_mode()

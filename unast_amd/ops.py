@@ -559,6 +559,58 @@ def embed_bwd(ids, dout, dE, T, shift_sos=-1, drop_p=0.0, seed=0, stream_id=0, n
              seed & 0xFFFFFFFF, stream_id, noise_p, noise_stream, _stream()), "unast_embed_bwd")
 
 
+# ---- the prefix slab of TextRNN's decoder training (csrc/prefix.hip); `lay` = unast_amd.train_rnn.prefix_tables(B, T, device) ---------------
+def prefix_bn_ws(lay, C, dev):
+    return torch.empty((lay.nchunks + lay.T) * 2 * C, dtype=torch.float64, device=dev)
+
+
+def prefix_bn_fwd(x2d, lay, gamma, beta, mean, rstd, varu, ws, y=None, p_last=None, running_mean=None, running_var=None, num_batches_tracked=None,
+                  eps=1e-5, momentum=0.1, drop_p=0.0, seed=0, stream_id=0):
+    rows, C = x2d.shape
+    if rows != lay.rows or not x2d.is_contiguous() or tuple(mean.shape) != (lay.T, C) or tuple(rstd.shape) != (lay.T, C) or tuple(varu.shape) != (lay.T, C):
+        raise ValueError("prefix_bn_fwd: x [slab rows, C] contiguous, mean / rstd / varu [T, C]")
+    if (y is not None and tuple(y.shape) != (rows, C)) or (p_last is not None and tuple(p_last.shape) != (lay.B, lay.T, C)) or ws.numel() < lay.nchunks * 2 * C:
+        raise ValueError("prefix_bn_fwd: y [slab rows, C] or p_last [B, T, C]; ws of nchunks*2*C doubles")
+    for t, n in ((x2d, "x"), (y, "y"), (p_last, "p_last"), (mean, "mean"), (rstd, "rstd"), (varu, "varu"), (gamma, "gamma"), (beta, "beta")):
+        _f32(t, n)
+    check(lib().unast_prefix_bn_fwd(_p(x2d), _p(lay.chunks), _p(lay.chunk_start), _p(lay.segoff), lay.nchunks, lay.rows, lay.B, lay.T, C, _p(gamma), _p(beta),
+                                    _p(y), _p(p_last), _p(mean), _p(rstd), _p(varu), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws),
+                                    eps, momentum, drop_p, seed & 0xFFFFFFFF, stream_id, _stream()), "unast_prefix_bn_fwd")
+
+
+def prefix_bn_bwd(dy, x2d, lay, mean, rstd, gamma, beta, dz, dgamma, dbeta, ws, last_only=False, drop_p=0.0, seed=0, stream_id=0):
+    rows, C = x2d.shape
+    want = (lay.B, lay.T, C) if last_only else (rows, C)
+    if rows != lay.rows or tuple(dy.shape) != want or tuple(dz.shape) != (rows, C) or not (dy.is_contiguous() and x2d.is_contiguous() and dz.is_contiguous()):
+        raise ValueError("prefix_bn_bwd: x, dz [slab rows, C], dy [slab rows, C] or (last_only) [B, T, C], contiguous")
+    if ws.numel() < (lay.nchunks + lay.T) * 2 * C or tuple(mean.shape) != (lay.T, C) or tuple(rstd.shape) != (lay.T, C):
+        raise ValueError("prefix_bn_bwd: ws of (nchunks + T)*2*C doubles, mean / rstd [T, C]")
+    for t, n in ((x2d, "x"), (dy, "dy"), (dz, "dz"), (mean, "mean"), (rstd, "rstd"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _f32(t, n)
+    check(lib().unast_prefix_bn_bwd(_p(dy), int(last_only), _p(x2d), _p(lay.chunks), _p(lay.chunk_start), _p(lay.segoff), lay.nchunks, lay.rows, lay.B, lay.T, C,
+                                    _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dz), _p(dgamma), _p(dbeta), _p(ws), drop_p, seed & 0xFFFFFFFF, stream_id,
+                                    _stream()), "unast_prefix_bn_bwd")
+
+
+def prefix_embed_fwd(target, E, lay, out, sos, drop_p=0.0, seed=0, stream_id=0):
+    if tuple(target.shape) != (lay.B, lay.T) or target.dtype is not torch.int64 or not target.is_contiguous() or tuple(out.shape) != (lay.rows, E.shape[1]):
+        raise ValueError("prefix_embed_fwd: target int64 [B, T] contiguous, out [slab rows, D]")
+    _f32(E, "E")
+    _f32(out, "out")
+    check(lib().unast_prefix_embed_fwd(_p(target), _p(E), _p(lay.chunks), _p(lay.segoff), lay.nchunks, lay.rows, lay.B, lay.T, E.shape[1], E.shape[0], sos,
+                                       _p(out), drop_p, seed & 0xFFFFFFFF, stream_id, _stream()), "unast_prefix_embed_fwd")
+
+
+def prefix_embed_bwd(dx, lay, G, drop_p=0.0, seed=0, stream_id=0):
+    D = dx.shape[1]
+    if tuple(dx.shape) != (lay.rows, D) or tuple(G.shape) != (lay.B, lay.T + 1, D) or not (dx.is_contiguous() and G.is_contiguous()):
+        raise ValueError("prefix_embed_bwd: dx [slab rows, D], G [B, T+1, D], contiguous")
+    _f32(dx, "dx")
+    _f32(G, "G")
+    check(lib().unast_prefix_embed_bwd(_p(dx), _p(lay.segoff), lay.rows, lay.B, lay.T, D, _p(G), drop_p, seed & 0xFFFFFFFF, stream_id, _stream()),
+          "unast_prefix_embed_bwd")
+
+
 def posenc_fwd(x2d, pe, y, T, scale, drop_p=0.0, seed=0, stream_id=0):
     rows, D = x2d.shape
     check(lib().unast_posenc_fwd(_p(x2d), _p(pe), _p(y), rows, T, D, scale, drop_p, seed & 0xFFFFFFFF, stream_id, _stream()), "unast_posenc_fwd")

@@ -19,6 +19,12 @@ SpeechRNN's decoder trains through two more entry points with the same conventio
     d_enc_output, d_h, d_c = decoder_backward(tape, d_pre, d_post, d_stop)  # writes p.grad of model.prenet, model.decoder, model.postnet
 
 so that the speech autoencoder is encoder_forward -> decoder_forward -> decoder_backward -> encoder_backward(..., accumulate=True).
+
+TextRNN's decoder trains through the last pair (the end of this file); both decoders run the same position loop
+(_loop_forward / _loop_backward), each supplying its own prenet rows and head:
+
+    tape = text_decoder_forward(model, target, enc_outputs, lens_k, seed=0) # tape.logits [B,T,len(symbols)], tape.sites
+    d_enc_output, d_h, d_c = text_decoder_backward(tape, d_logits)          # writes p.grad of model.prenet, model.decoder, model.postnet
 """
 import collections
 
@@ -352,20 +358,19 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
 # ==== SpeechRNN decoder: teacher-forced train-mode decode_sequence (src/network.py:352-377) and its backward; DESIGN 5j ============================
 S_DPRE, S_DDROP, S_DOUT, S_POST = 8, 9, 10, 11      # decoder prenet dropout, nn.LSTM inter-layer, dropout1, the four post-net dropouts (11..14)
 
-class DecoderPack:
-    """The operands the decoder's train kernels read, derived from the parameters of model.prenet, model.decoder and model.postnet: the
+class _LoopPack:
+    """The operands of the position loop both decoders share (RNNDecoder: the attention layer, the two LSTM cells, the projection): the
     fp32-level weight pairs of the many-row contractions, and the transposed weights the per-position input-gradient contractions
     (unast_rnn_linear: Y = X W^T) take as their W."""
 
-    def __init__(self, m):
-        dec, po, pn = m.decoder, m.postnet, m.prenet.layer
+    def __init__(self, m, what):
+        dec = m.decoder
         if dec.num_layers != 2 or dec.attention not in ("luong", "lsa"):
-            raise NotImplementedError("decoder_forward: two decoder layers with 'luong' or 'lsa' attention (what the eval path supports)")
-        self.fcs = [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (pn.fc1, pn.fc2)]
+            raise NotImplementedError("%s: two decoder layers with 'luong' or 'lsa' attention (what the eval path supports)" % what)
         r = dec.rnn
         w0 = r.weight_ih_l0.detach()
         if tuple(w0.shape) != (1024, 768) or tuple(r.weight_ih_l1.shape) != (1024, 256):
-            raise NotImplementedError("decoder_forward: hidden = e_in = 256 with a 512-wide encoder output")
+            raise NotImplementedError("%s: hidden = e_in = 256 with a 512-wide encoder output" % what)
         self.w_ih0_p, self.w_ih0_c = _resid(w0[:, :256]), _c(w0[:, 256:])                   # the prenet columns (batched) and the context columns
         self.w_hh0, self.w_ih1, self.w_hh1 = _c(r.weight_hh_l0), _c(r.weight_ih_l1), _c(r.weight_hh_l1)
         self.bias = [_c(getattr(r, n)) for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1")]
@@ -384,9 +389,19 @@ class DecoderPack:
         self.Wq, self.Wmem, self.v = _c(self.q_lin.weight), _resid(self.mem_lin.weight), _c(self.v_lin.weight).view(-1)
         self.A = self.Wq.shape[0]
         if self.A % 4 or self.A > 64:
-            raise NotImplementedError("decoder_forward: attn_dim must be a multiple of 4, at most 64 (got %d)" % self.A)
+            raise NotImplementedError("%s: attn_dim must be a multiple of 4, at most 64 (got %d)" % (what, self.A))
         self.proj_lin = dec.linear_projection.linear_layer
         self.proj = (_resid(self.proj_lin.weight), _c(self.proj_lin.bias))
+
+
+class DecoderPack(_LoopPack):
+    """SpeechRNN: the loop's operands plus the prenet's two linears, the [linear_project | stop_linear] head and the post-net."""
+
+    def __init__(self, m):
+        super().__init__(m, "decoder_forward")
+        po, pn = m.postnet, m.prenet.layer
+        w0 = self.w_hh0
+        self.fcs = [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (pn.fc1, pn.fc2)]
         M = po.linear_project.weight.shape[0]
         self.M, self.ldh = M, (M + 1 + 3) // 4 * 4                                          # [linear_project | stop_linear | zero rows] as one head
         Wh = torch.zeros(self.ldh, 256, dtype=_F32, device=w0.device)
@@ -405,7 +420,31 @@ def _decoder_params(model):
     return list(model.prenet.parameters()) + list(model.decoder.parameters()) + list(model.postnet.parameters())
 
 
-def decoder_pack_of(m):
+class TextDecoderPack(_LoopPack):
+    """TextRNN: the loop's operands plus the prefix prenet's embedding, convs and BatchNorms and the TextPostnet head (fc1, rows padded to a
+    multiple of 4 with zeros)."""
+
+    def __init__(self, m):
+        super().__init__(m, "text_decoder_forward")
+        pn, fc = m.prenet, m.postnet.fc1
+        self.emb = _c(pn.embed.weight)
+        self.convs = [(_resid(getattr(pn, "conv%d" % i).conv.weight.detach().permute(0, 2, 1)), _c(getattr(pn, "conv%d" % i).conv.bias),
+                       getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+        E = self.emb.shape[1]
+        if E % 4 or 256 % (E // 4) or any(tuple(wp[0].shape[::2]) != (256, cin) or wp[0].shape[1] != 5 for (wp, _, _, _), cin in zip(self.convs, (E, 256, 256))):
+            raise NotImplementedError("text_decoder_forward: three 5-tap convs into 256 channels over an embedding whose width / 4 divides 256")
+        if tuple(fc.weight.shape[1:]) != (256,):
+            raise NotImplementedError("text_decoder_forward: TextPostnet.fc1 over 256 features")
+        self.V = fc.weight.shape[0]
+        self.ldh = (self.V + 3) // 4 * 4
+        Wh = torch.zeros(self.ldh, 256, dtype=_F32, device=self.emb.device)
+        bh = torch.zeros(self.ldh, dtype=_F32, device=self.emb.device)
+        Wh[:self.V].copy_(fc.weight.detach())
+        bh[:self.V].copy_(fc.bias.detach())
+        self.head = (_resid(Wh), bh)
+
+
+def decoder_pack_of(m, cls=DecoderPack):
     ver, dev = 0, None
     for t in _decoder_params(m):
         ver += t._version
@@ -413,7 +452,7 @@ def decoder_pack_of(m):
     key = (ver, dev)
     cached = m.__dict__.get("_rnn_decoder_train_pack")
     if cached is None or cached[0] != key:
-        cached = (key, DecoderPack(m))
+        cached = (key, cls(m))
         m.__dict__["_rnn_decoder_train_pack"] = cached
     return cached[1]
 
@@ -449,41 +488,19 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     from .network import TextRNN, SpeechRNN
     if isinstance(model, TextRNN):
         raise NotImplementedError("decoder_forward: SpeechRNN only -- TextRNN.decode runs TextPrenet over the whole prefix at every position "
-                                  "(batch-statistics BatchNorm over B*(i+1) rows and a running-statistics update per position, O(T^2))")
+                                  "(batch-statistics BatchNorm over the prefix's rows and a running-statistics update per position, O(T^2)): "
+                                  "text_decoder_forward / text_decoder_backward train it")
     if not isinstance(model, SpeechRNN):
         raise TypeError("decoder_forward: model must be a unast_amd.network.SpeechRNN")
     if not model.training:
         raise RuntimeError("decoder_forward is the train-mode entry point: call model.train() first (model.decode_sequence() is the eval forward)")
-    if isinstance(enc_outputs, Tape):
-        enc_outputs = (enc_outputs.hidden, enc_outputs.enc_output)
     mel = model._mel(target)
-    (h0, c0), enc = enc_outputs
     B, T, M = mel.shape
-    if T < 1 or not (torch.is_tensor(enc) and enc.is_cuda and enc.dim() == 3 and enc.shape[0] == B and enc.shape[2] == 512):
-        raise ValueError("decoder_forward: enc_output must be a CUDA tensor [B,Tk,512] with target's B, T >= 1")
-    Tk = enc.shape[1]
-    if not 1 <= Tk <= 2048:
-        raise ValueError("decoder_forward: 1 <= Tk <= 2048 (got %d)" % Tk)
-    for t, n in ((h0, "h"), (c0, "c")):
-        if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == (2, B, 256)):
-            raise ValueError("decoder_forward: %s must be a CUDA tensor [2,B,256]" % n)
-    lens_l = [int(v) for v in (lens_k.tolist() if hasattr(lens_k, "tolist") else lens_k)]
-    if len(lens_l) != B or min(lens_l) < 1 or max(lens_l) > Tk:
-        raise ValueError("decoder_forward: lens_k must hold one length in 1..Tk = %d per sequence (got %r)" % (Tk, lens_l))
-    if next(model.parameters()).device.type != "cuda":
-        raise RuntimeError("unast_amd runs on the GPU only: move the model to a CUDA (ROCm) device first; there is no CPU path")
-    dev = mel.device
-    P = decoder_pack_of(model)
-    enc, h0, c0 = (t.detach().to(_F32).contiguous() for t in (enc, h0, c0))
-    lens = torch.tensor(lens_l, dtype=torch.int32, device=dev)
-    tape = DecoderTape()
-    tape.model, tape.P, tape.lens, tape.B, tape.T, tape.Tk = model, P, lens, B, T, Tk
-    tape.seed, tape.epoch = int(seed), ops.rng_epoch_counter().clone()
-    tape.enc, tape.h0, tape.c0 = enc, h0, c0
-    N, A, lsa = B * T, P.A, P.mode == ops.ATTN_LSA
-    p_pre, p_dec, p_post = float(model.prenet.p), float(model.decoder.p), float(model.postnet.p)
+    tape = _begin_decoder_tape("decoder_forward", model, DecoderPack, enc_outputs, lens_k, B, T, seed, mel.device)
+    P, N = tape.P, B * T
+    p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
 
-    # ---- batched before the loop: the prenet on all fed frames, W_ih_l0[:, :256] P + b_ih, the memory-side projection ----------------------
+    # ---- batched before the loop: the prenet on all fed frames ------------------------------------------------------------------------------
     feed = ops.shift_frames(mel, torch.empty_like(mel)).view(N, M)                          # feed_0 = 0, feed_i = target[:, i-1]
     (w1, b1, _), (w2, b2, _) = P.fcs
     a1 = _linear_rows(feed, w1, b1)
@@ -491,9 +508,81 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     ops.leaky_dropout(a1, None, h1, 0.0, p_pre, seed, S_DPRE)
     tape.site("d_prenet_dropout", p_pre, S_DPRE, N, a1.shape[1])
     pre = _linear_rows(h1, w2, b2, act=1)
+    tape.feed, tape.a1, tape.h1 = feed, a1, h1
+    o = _loop_forward(tape, pre, mark)
+
+    # ---- batched after the loop: the head, the post-net -----------------------------------------------------------------------------------------
+    dev = mel.device
+    head = _linear_rows(o, P.head[0], P.head[1]).view(B, T, P.ldh)
+    outs = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)                                 # position 0 = the all-zero go frame
+    outs[:, 1:].copy_(head[:, :, :M])
+    tape.stop = head[:, :, M].contiguous()
+    N1 = B * (T + 1)
+    tape.xs, tape.zs = [outs.view(N1, M)], []
+    tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
+    bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
+    cur = outs
+    for k, (wp, bias, _, bn) in enumerate(P.post):
+        _check_bn(bn, "decoder_forward")
+        z = _conv(cur, wp, bias, 4).view(N1, 256)
+        y = _buf(N1, 256, dev=dev)
+        ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, 2, drop_p=p_post, seed=seed,
+                   stream_id=S_POST + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
+        tape.site("post_dropout%d" % k, p_post, S_POST + k, N1, 256)
+        tape.zs.append(z)
+        tape.xs.append(y)
+        cur = y.view(B, T + 1, 256)
+    post = _conv(cur, P.post_out[0], P.post_out[1], 4)
+    ops.add_inplace(post, outs)
+    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    tape.pre, tape.post = outs[:, 1:], post[:, 1:]
+    return tape
+
+
+def _check_bn(bn, what):
+    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+        raise NotImplementedError("%s: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)" % what)
+
+
+def _begin_decoder_tape(what, model, pack_cls, enc_outputs, lens_k, B, T, seed, dev):
+    """The memory-side checks and the tape header both decoder entry points share."""
+    if isinstance(enc_outputs, Tape):
+        enc_outputs = (enc_outputs.hidden, enc_outputs.enc_output)
+    (h0, c0), enc = enc_outputs
+    if T < 1 or not (torch.is_tensor(enc) and enc.is_cuda and enc.dim() == 3 and enc.shape[0] == B and enc.shape[2] == 512):
+        raise ValueError("%s: enc_output must be a CUDA tensor [B,Tk,512] with target's B, T >= 1" % what)
+    Tk = enc.shape[1]
+    if not 1 <= Tk <= 2048:
+        raise ValueError("%s: 1 <= Tk <= 2048 (got %d)" % (what, Tk))
+    for t, n in ((h0, "h"), (c0, "c")):
+        if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == (2, B, 256)):
+            raise ValueError("%s: %s must be a CUDA tensor [2,B,256]" % (what, n))
+    lens_l = [int(v) for v in (lens_k.tolist() if hasattr(lens_k, "tolist") else lens_k)]
+    if len(lens_l) != B or min(lens_l) < 1 or max(lens_l) > Tk:
+        raise ValueError("%s: lens_k must hold one length in 1..Tk = %d per sequence (got %r)" % (what, Tk, lens_l))
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError("unast_amd runs on the GPU only: move the model to a CUDA (ROCm) device first; there is no CPU path")
+    P = decoder_pack_of(model, pack_cls)
+    enc, h0, c0 = (t.detach().to(_F32).contiguous() for t in (enc, h0, c0))
+    tape = DecoderTape()
+    tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.entry = model, P, B, T, Tk, what
+    tape.lens = torch.tensor(lens_l, dtype=torch.int32, device=dev)
+    tape.seed, tape.epoch = int(seed), ops.rng_epoch_counter().clone()
+    tape.enc, tape.h0, tape.c0 = enc, h0, c0
+    return tape
+
+
+def _loop_forward(tape, pre, mark):
+    """RNNDecoder over all positions, shared by both decoders: pre [B*T,256] = the prenet's row for every position (with teacher forcing it
+    does not depend on the recurrence).  Hoists W_ih_l0[:, :256] pre + b_ih and the memory-side projection, runs the position loop, then
+    the projection + tanh + dropout1 for all positions.  Keeps the loop's state on the tape; returns o [B*T,256], the head's input."""
+    model, P, B, T, Tk, seed, lens, enc, h0, c0 = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens, tape.enc, tape.h0, tape.c0
+    dev = enc.device
+    N, A, lsa = B * T, P.A, P.mode == ops.ATTN_LSA
+    p_dec = float(model.decoder.p)
     xp0 = _linear_rows(pre, P.w_ih0_p, P.bias[0]).view(B, T, 1024)
     mem = _linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, A)
-    tape.feed, tape.a1, tape.h1, tape.pre_act, tape.mem = feed, a1, h1, pre, mem
+    tape.pre_act, tape.mem = pre, mem
 
     # ---- the loop: per position 7 launches on host-indexed slices of [B,T,...] slabs -------------------------------------------------------------
     Tkp = (Tk + 3) // 4 * 4
@@ -525,38 +614,15 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
         mark("loop_end")
     tape.W, tape.CUM, tape.HC, tape.H0, tape.H0d, tape.S0, tape.S1, tape.F1 = W, CUM, HC, H0, H0d, S0, S1, F1
 
-    # ---- batched after the loop: projection + tanh + dropout1, the head, the post-net ------------------------------------------------------------
+    # ---- batched after the loop: projection + tanh + dropout1 ------------------------------------------------------------------------------------
     tz = ops.tanh_rows(_linear_rows(HC.view(N, 768), P.proj[0], P.proj[1]))
     o = tz
     if p_dec > 0.0:
         o = torch.empty_like(tz)
         ops.leaky_dropout(tz, None, o, 1.0, p_dec, seed, S_DOUT)
     tape.site("d_dropout1", p_dec, S_DOUT, N, 256)
-    head = _linear_rows(o, P.head[0], P.head[1]).view(B, T, P.ldh)
-    outs = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)                                 # position 0 = the all-zero go frame
-    outs[:, 1:].copy_(head[:, :, :M])
-    tape.tz, tape.o, tape.stop = tz, o, head[:, :, M].contiguous()
-    N1 = B * (T + 1)
-    tape.xs, tape.zs = [outs.view(N1, M)], []
-    tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
-    bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
-    cur = outs
-    for k, (wp, bias, _, bn) in enumerate(P.post):
-        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-            raise NotImplementedError("decoder_forward: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)")
-        z = _conv(cur, wp, bias, 4).view(N1, 256)
-        y = _buf(N1, 256, dev=dev)
-        ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, 2, drop_p=p_post, seed=seed,
-                   stream_id=S_POST + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
-        tape.site("post_dropout%d" % k, p_post, S_POST + k, N1, 256)
-        tape.zs.append(z)
-        tape.xs.append(y)
-        cur = y.view(B, T + 1, 256)
-    post = _conv(cur, P.post_out[0], P.post_out[1], 4)
-    ops.add_inplace(post, outs)
-    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
-    tape.pre, tape.post = outs[:, 1:], post[:, 1:]
-    return tape
+    tape.tz, tape.o = tz, o
+    return o
 
 
 def _conv_grads(dz2d, x2d, B, T, wpair, conv, pad_left):
@@ -591,20 +657,20 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     zero).  Writes p.grad of exactly the parameters under model.prenet, model.decoder and model.postnet (overwritten, or added to with
     accumulate=True; an existing dense fp32 .grad is kept in place).  Returns (d_enc_output [B,Tk,512], d_h, d_c [2,B,256]), the cotangents
     encoder_backward takes.  A tape is used once.  mark: as decoder_forward's."""
-    if not isinstance(tape, DecoderTape):
+    if not isinstance(tape, DecoderTape) or getattr(tape, "entry", "decoder_forward") != "decoder_forward":
         raise TypeError("decoder_backward: tape must come from decoder_forward")
     if tape.used:
         raise RuntimeError("decoder_backward: this tape has been used; run decoder_forward again")
-    model, P, B, T, Tk, seed, lens = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens
-    M, A, ldh, lsa = P.M, P.A, P.ldh, P.mode == ops.ATTN_LSA
+    model, P, B, T, seed = tape.model, tape.P, tape.B, tape.T, tape.seed
+    M, ldh = P.M, P.ldh
     N, N1 = B * T, B * (T + 1)
     dev = tape.enc.device
     d_pre, d_post = _cot(d_pre, (B, T, M), "d_pre", dev, "decoder_backward"), _cot(d_post, (B, T, M), "d_post", dev, "decoder_backward")
     d_stop = _cot(d_stop, (B, T), "d_stop", dev, "decoder_backward")
     tape.used = True
     _prepare_grads(_decoder_params(model), accumulate)
-    po, dec = model.postnet, model.decoder
-    p_pre, p_dec, p_post = float(model.prenet.p), float(dec.p), float(po.p)
+    po = model.postnet
+    p_pre, p_post = float(model.prenet.p), float(po.p)
 
     # ---- batched before the loop: the post-net into d_outputs, the head, dropout1, tanh, the projection -----------------------------------------
     d_head = torch.zeros(B, T, ldh, dtype=_F32, device=dev)
@@ -633,6 +699,30 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     po.stop_linear.weight.grad.add_(gW[M:M + 1])
     po.stop_linear.bias.grad.add_(gb[M:M + 1])
     d_o = _dgrad_rows(dhp, P.head[0], _buf(N, 256, dev=dev))
+    dg0p, d_enc, d_h, d_c = _loop_backward(tape, d_o, mark)
+    # the prenet (shared with the encoder)
+    d_p = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev))
+    (w1, _, fc1), (w2, _, fc2) = P.fcs
+    ops.relu_bwd(d_p, tape.pre_act)
+    dpp = _parts(d_p)
+    _wgrad_rows(dpp, ALL, tape.h1, _resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
+    dh1p = _dgrad_rows(dpp, w2, _buf(N, tape.h1.shape[1], dev=dev))
+    da1 = torch.empty_like(dh1p)
+    ops.leaky_dropout(tape.a1, dh1p, da1, 0.0, p_pre, seed, S_DPRE)
+    _wgrad_rows(_parts(da1), ALL, tape.feed, _resid_of(tape.feed), fc1.weight.grad, (fc1.bias.grad,))
+    return d_enc, d_h, d_c
+
+
+def _loop_backward(tape, d_o, mark):
+    """Backward of _loop_forward, shared by both decoders: d_o [B*T,256] = the gradient of the head's input.  Writes the gradients of
+    model.decoder's parameters (all of W_ih_l0 included: its first 256 columns contract with the prenet rows on the tape).  Returns
+    (dg0p, d_enc_output, d_h, d_c): dg0p = _parts of layer 0's gate gradients [B*T,1024] -- the caller's prenet gradient is
+    dg0p . W_ih_l0[:, :256] -- and the three cotangents encoder_backward takes."""
+    model, P, B, T, Tk, seed, lens = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens
+    A, lsa, N = P.A, P.mode == ops.ATTN_LSA, B * T
+    dev = tape.enc.device
+    dec = model.decoder
+    p_dec = float(dec.p)
     if p_dec > 0.0:
         d_od = torch.empty_like(d_o)
         ops.leaky_dropout(d_o, d_o, d_od, 1.0, p_dec, seed, S_DOUT)                         # slope 1: the mask and its 1/(1-p) only
@@ -691,16 +781,6 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     if lsa:
         _add_over_b(dd_part, P.dense_lin.weight.grad)
         _add_over_b(dcv_part, P.conv_mod.weight.grad)
-    # the prenet (shared with the encoder)
-    d_p = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev))
-    (w1, _, fc1), (w2, _, fc2) = P.fcs
-    ops.relu_bwd(d_p, pre)
-    dpp = _parts(d_p)
-    _wgrad_rows(dpp, ALL, tape.h1, _resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
-    dh1p = _dgrad_rows(dpp, w2, _buf(N, tape.h1.shape[1], dev=dev))
-    da1 = torch.empty_like(dh1p)
-    ops.leaky_dropout(tape.a1, dh1p, da1, 0.0, p_pre, seed, S_DPRE)
-    _wgrad_rows(_parts(da1), ALL, tape.feed, _resid_of(tape.feed), fc1.weight.grad, (fc1.bias.grad,))
     # the memory side: dW_mem = d_mem^T enc, d_enc = d_mem W_mem + per sequence w_b^T [Tk,T] . d_ctx_b [T,512] (formed once, after the loop)
     enc2 = tape.enc.view(B * Tk, 512)
     dmp = _parts(d_mem.view(B * Tk, A))
@@ -710,4 +790,190 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     dctx_res = _resid_of(DCTX)
     for b in range(B):
         _wgrad_rows(tuple(t[b] for t in wparts), slice(0, Tk), DCTX[b], dctx_res[b], d_enc[b])
-    return d_enc, torch.stack([dh0, dh1]), torch.stack([dc0, dc1])
+    return dg0p, d_enc, torch.stack([dh0, dh1]), torch.stack([dc0, dc1])
+
+
+# ==== TextRNN decoder: teacher-forced train-mode decode_sequence (src/network.py:539-575) and its backward; DESIGN 5k ==============================
+# TextRNN.decode runs TextPrenet over the whole prefix at every position and keeps the last row: position 0 sees [SOS], position i >= 1 sees
+# target[:, :i] (no SOS), each call with its own dropout masks, its own batch statistics over the B * L_i rows of that prefix (PAD included) and
+# its own running-statistics update.  All prefixes are computed before the loop in one slab of rows (prefix_layout); csrc/prefix.hip.
+S_TEMB, S_TPRE, S_TPOST = 16, 17, 20               # the slab's emb_dropout, dropout1..3 (17..19), TextPostnet.dropout1
+GAP = 2                                            # zero rows after every sequence of the slab: a 5-tap conv's padding on either side
+MAX_SLAB_BYTES = 0x7FFFFFF0                        # rows * 256 channels * 4 bytes: the kernels' 32-bit row arithmetic and buffer ranges
+
+PrefixLayout = collections.namedtuple("PrefixLayout", "off lens total")
+
+
+def prefix_layout(B, T):
+    """The prefix slab's geometry.  Segment s = 0..T-1 is position s's prenet input: B sequences of lens[s] = max(s, 1) live rows ([SOS] at
+    s = 0, target[b, 0:s] after that), each followed by GAP = 2 zero rows, sequences b = 0..B-1 back to back:
+
+        row(s, b, j) = off[s] + b * (lens[s] + GAP) + j,   0 <= j < lens[s] live,   j = lens[s], lens[s] + 1 the gap
+
+    Segments follow one another without further padding (off[s+1] = off[s] + B * (lens[s] + GAP)); total = off[T-1] + B * (lens[T-1] + GAP) rows.
+    Read as ONE sequence of `total` rows, the slab gives a 5-tap 'same' convolution exactly the zero padding every prefix had on its own."""
+    if B < 1 or T < 1:
+        raise ValueError("prefix_layout: B >= 1 and T >= 1")
+    lens = [max(s, 1) for s in range(T)]
+    off, r = [], 0
+    for L in lens:
+        off.append(r)
+        r += B * (L + GAP)
+    return PrefixLayout(off, lens, r)
+
+
+_PREFIX_TABLES = {}
+PrefixTables = collections.namedtuple("PrefixTables", "B T rows nchunks segoff chunks chunk_start")
+PREFIX_CHUNK = 64                                  # rows per workgroup of the slab kernels (csrc/prefix.hip PFX_CHUNK)
+
+
+def prefix_tables(B, T, dev):
+    """The device-side tables of csrc/prefix.hip for prefix_layout(B, T): segoff [T+1], chunks [nchunks, 2] = {segment, first row} of runs of
+    at most 64 rows that stay inside one segment, chunk_start [T+1] = the first chunk of each segment."""
+    key = (B, T, str(dev))
+    t = _PREFIX_TABLES.get(key)
+    if t is None:
+        lay = prefix_layout(B, T)
+        chunks, start = [], []
+        for s in range(T):
+            start.append(len(chunks))
+            end = lay.off[s] + B * (lay.lens[s] + GAP)
+            chunks.extend((s, r) for r in range(lay.off[s], end, PREFIX_CHUNK))
+        start.append(len(chunks))
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)                          # noqa: E731
+        if len(_PREFIX_TABLES) >= 16:
+            _PREFIX_TABLES.clear()
+        t = _PREFIX_TABLES[key] = PrefixTables(B, T, lay.total, len(chunks), i32(lay.off + [lay.total]), i32(chunks).view(-1, 2).contiguous(), i32(start))
+    return t
+
+
+@torch.no_grad()
+def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
+    """Train-mode, teacher-forced TextRNN.decode_sequence (teacher_ratio = 1): target [B,T] int64 on the GPU, enc_outputs = ((h, c)
+    [2,B,256], enc_output [B,Tk,512]) or an encoder Tape of either side, lens_k the live keys per sequence (1..Tk).  2 <= B (one row cannot be
+    normalised: the reference raises at position 0), 1 <= T <= 512.  Returns a DecoderTape: .logits [B,T,len(symbols)].  Updates the prenet's
+    BatchNorm running statistics T times each (num_batches_tracked += T) and drops the model's cached eval operands.  mark (optional): called
+    with 'prefix_begin' / 'prefix_end' around the prefix prenet and 'loop_begin' / 'loop_end' around the position loop."""
+    from .network import TextRNN
+    from .utils import SOS_IDX
+    if not isinstance(model, TextRNN):
+        raise TypeError("text_decoder_forward: model must be a unast_amd.network.TextRNN (decoder_forward trains a SpeechRNN)")
+    if not model.training:
+        raise RuntimeError("text_decoder_forward is the train-mode entry point: call model.train() first (model.decode_sequence() is the eval forward)")
+    if not torch.is_tensor(target) or target.dim() != 2:
+        raise ValueError("text_decoder_forward: target must be an int64 tensor [B,T]")
+    B, T = target.shape
+    if B < 2:
+        raise ValueError("text_decoder_forward: B >= 2 -- position 0 normalises B rows with batch statistics, one row cannot be normalised "
+                         "(the reference raises 'Expected more than 1 value per channel')")
+    if not 1 <= T <= 512:
+        raise ValueError("text_decoder_forward: 1 <= T <= 512 (got %d)" % T)
+    lay = prefix_layout(B, T)
+    if lay.total * 256 * 4 >= MAX_SLAB_BYTES:
+        raise ValueError("text_decoder_forward: the prefix slab of B = %d, T = %d has %d rows; rows * 1024 bytes must stay below 2 GiB" % (B, T, lay.total))
+    ids = model._ids(target)
+    dev = ids.device
+    tape = _begin_decoder_tape("text_decoder_forward", model, TextDecoderPack, enc_outputs, lens_k, B, T, seed, dev)
+    P, N, R = tape.P, B * T, lay.total
+    ids = model._ids(ids, P).contiguous()
+    tabs = prefix_tables(B, T, dev)
+    p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
+
+    # ---- the prefix prenet: every stage once over the slab ------------------------------------------------------------------------------------
+    if mark is not None:
+        mark("prefix_begin")
+    E = P.emb.shape[1]
+    x0 = _buf(R, E, dev=dev)
+    ops.prefix_embed_fwd(ids, P.emb, tabs, x0, SOS_IDX, drop_p=p_pre, seed=seed, stream_id=S_TEMB)
+    tape.site("t_emb_dropout", p_pre, S_TEMB, R, E)
+    tape.ids, tape.tabs = ids, tabs
+    tape.xs, tape.zs = [x0], []
+    tape.mean, tape.rstd = _buf(3, T, 256, dev=dev), _buf(3, T, 256, dev=dev)
+    varu = _buf(T, 256, dev=dev)
+    ws = ops.prefix_bn_ws(tabs, 256, dev)
+    pre = _buf(B, T, 256, dev=dev)
+    cur = x0
+    for i, (wp, bias, _, bn) in enumerate(P.convs):
+        _check_bn(bn, "text_decoder_forward")
+        z = _conv(cur.view(1, R, -1), wp, bias, 2).view(R, 256)                             # the gaps are every neighbour's zero padding
+        y = _buf(R, 256, dev=dev) if i < 2 else None
+        ops.prefix_bn_fwd(z, tabs, bn.weight, bn.bias, tape.mean[i], tape.rstd[i], varu, ws, y=y, p_last=pre if i == 2 else None,
+                          running_mean=bn.running_mean, running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked, eps=bn.eps,
+                          momentum=bn.momentum, drop_p=p_pre, seed=seed, stream_id=S_TPRE + i)
+        tape.site("t_dropout%d" % (i + 1), p_pre, S_TPRE + i, R, 256)
+        tape.zs.append(z)
+        if y is not None:
+            tape.xs.append(y)
+            cur = y
+    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    if mark is not None:
+        mark("prefix_end")
+
+    o = _loop_forward(tape, pre.view(N, 256), mark)
+
+    # ---- TextPostnet: its own dropout1 on top of the decoder's, then fc1 ---------------------------------------------------------------------------
+    o2 = o
+    if p_post > 0.0:
+        o2 = torch.empty_like(o)
+        ops.leaky_dropout(o, None, o2, 1.0, p_post, seed, S_TPOST)
+    tape.site("t_post_dropout", p_post, S_TPOST, N, 256)
+    tape.o2 = o2
+    tape.logits = _linear_rows(o2, P.head[0], P.head[1]).view(B, T, P.ldh)[:, :, :P.V].contiguous()
+    return tape
+
+
+@torch.no_grad()
+def text_decoder_backward(tape, d_logits, accumulate=False, mark=None):
+    """Backward of text_decoder_forward for the scalar whose gradient with respect to logits [B,T,V] is given.  Writes p.grad of exactly the
+    parameters under model.prenet, model.decoder and model.postnet (overwritten, or added to with accumulate=True; an existing dense fp32
+    .grad is kept in place).  Returns (d_enc_output [B,Tk,512], d_h, d_c [2,B,256]), the cotangents encoder_backward takes.  A tape is used once.
+    mark: as text_decoder_forward's."""
+    from .utils import SOS_IDX
+    if not isinstance(tape, DecoderTape) or getattr(tape, "entry", None) != "text_decoder_forward":
+        raise TypeError("text_decoder_backward: tape must come from text_decoder_forward")
+    if tape.used:
+        raise RuntimeError("text_decoder_backward: this tape has been used; run text_decoder_forward again")
+    model, P, B, T, seed, tabs = tape.model, tape.P, tape.B, tape.T, tape.seed, tape.tabs
+    N, R, V, ldh = B * T, tabs.rows, P.V, P.ldh
+    dev = tape.enc.device
+    d_logits = _cot(d_logits, (B, T, V), "d_logits", dev, "text_decoder_backward")
+    if d_logits is None:
+        raise ValueError("text_decoder_backward: d_logits must be a float32 CUDA tensor %s" % ((B, T, V),))
+    tape.used = True
+    _prepare_grads(_decoder_params(model), accumulate)
+    p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
+    fc = model.postnet.fc1
+
+    d_head = torch.zeros(B, T, ldh, dtype=_F32, device=dev)
+    d_head[:, :, :V].copy_(d_logits)
+    dhp = _parts(d_head.view(N, ldh))
+    gW, gb = torch.zeros(ldh, 256, dtype=_F32, device=dev), torch.zeros(ldh, dtype=_F32, device=dev)
+    _wgrad_rows(dhp, ALL, tape.o2, _resid_of(tape.o2), gW, (gb,))
+    fc.weight.grad.add_(gW[:V])
+    fc.bias.grad.add_(gb[:V])
+    d_o = _dgrad_rows(dhp, P.head[0], _buf(N, 256, dev=dev))
+    if p_post > 0.0:
+        d_od = torch.empty_like(d_o)
+        ops.leaky_dropout(d_o, d_o, d_od, 1.0, p_post, seed, S_TPOST)
+        d_o = d_od
+    dg0p, d_enc, d_h, d_c = _loop_backward(tape, d_o, mark)
+
+    # ---- the prefix prenet: d_P sits on each prefix's last row and spreads through the statistics to every row of the prefix -------------------------
+    if mark is not None:
+        mark("prefix_begin")
+    dy = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev)).view(B, T, 256)
+    ws = ops.prefix_bn_ws(tabs, 256, dev)
+    for i in (2, 1, 0):
+        wpair, _, conv, bn = P.convs[i]
+        dz = _buf(R, 256, dev=dev)
+        ops.prefix_bn_bwd(dy, tape.zs[i], tabs, tape.mean[i], tape.rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, ws, last_only=(i == 2),
+                          drop_p=p_pre, seed=seed, stream_id=S_TPRE + i)
+        dy = _conv_grads(dz, tape.xs[i], 1, R, wpair, conv, 2)                              # its gap rows hold the neighbours' spill: nobody reads them
+    emb = model.prenet.embed
+    G = _buf(B, T + 1, dy.shape[1], dev=dev)
+    ops.prefix_embed_bwd(dy, tabs, G, drop_p=p_pre, seed=seed, stream_id=S_TEMB)
+    ids_ext = torch.cat([torch.full((B, 1), SOS_IDX, dtype=torch.int64, device=dev), tape.ids], 1).contiguous()
+    ops.embed_bwd(ids_ext, G.view(B * (T + 1), -1), emb.weight.grad, T + 1, padding_idx=emb.padding_idx if emb.padding_idx is not None else -1)
+    if mark is not None:
+        mark("prefix_end")
+    return d_enc, d_h, d_c

@@ -10,7 +10,10 @@ teacher-forced position of the same session as the yardstick, unast_rnn_attn_ste
 --train-text-decoder: TextRNN decoder training at T = 180, B in {4, 16, 32}, Tk in {180, 800}, both attention types (dropout on) --
 text_decoder_forward, forward + backward, the prefix prenet's share, the loops' per-position times next to SpeechRNN's at the same shapes, the
 saved bytes, and the prefix prenet issued position by position through the uniform-[B,T] entry points as the comparator of the slab form.
-Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder]"""
+--train-step: the whole train step of the family (unast_amd.train_rnn_step through unast_amd.train's entry points, dropout, noise, SpecAugment
+and the drawn permutation on) at T_text = 180, T_mel = 800, B in {4, 16}, both attention types -- ms per AE / SP / D sub-step and per
+optimizer step of each phase, one warm-up round and medians of 5.
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder | --train-step]"""
 import argparse
 import os
 import statistics
@@ -31,6 +34,7 @@ ap.add_argument("--frames", type=int, default=800)
 ap.add_argument("--train", action="store_true")
 ap.add_argument("--train-decoder", action="store_true")
 ap.add_argument("--train-text-decoder", action="store_true")
+ap.add_argument("--train-step", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -259,6 +263,50 @@ def train_text_decoder_mode():
                       "comparator %.1f ms" % (Bb, T, lay.total, lay.total - 2 * Bb * T, pf + pb, loop))
 
 
+def train_step_mode():
+    import json
+    from collections import defaultdict
+    from types import SimpleNamespace
+    from unast_amd import train
+    train.DEVICE = D
+    cfgs = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "rnn_configs.json")))
+    for attn in ("luong", "lsa"):
+        for Bb in (4, 16):
+            args = SimpleNamespace(**dict(cfgs["rnn_d_" + attn], load_path=None, ae_steps=1, sp_steps=1, cm_steps=0, d_steps=1, train_batch_size=Bb))
+            train.set_seed(0)
+            _, _, model, opt, _ = train.initialize_model(args)
+            model.train()
+            getter = train.SyntheticBatchGetter(args, t_text=TT, t_mel=TM)
+            times, losses = defaultdict(list), defaultdict(list)
+
+            def timed(name, fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1))
+            for rep in range(6):                                                                  # one warm-up round, five measured
+                if rep == 1:
+                    times.clear()
+                b_ae, b_sp, b_d = getter._next(), getter._next(), getter._next()
+                train.freeze_model_parameters(model.discriminator)
+                timed("ae", lambda: train.train_ae_step(losses, model, b_ae, 0, 2, args))
+                timed("sp", lambda: train.train_sp_step(losses, model, b_sp, 0, 2, args))
+                timed("opt_gen", lambda: train.optimizer_step(model, opt, args))
+                train.unfreeze_model_parameters(model.discriminator)
+                timed("d", lambda: train.train_discriminator_step(losses, model, b_d, 0, 1, args))
+                timed("opt_disc", lambda: train.optimizer_step(model, opt, args))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            assert all(bool(torch.isfinite(v)) for vs in losses.values() for v in vs)
+            print("[%s] B=%d T_text=%d T_mel=%d: AE sub-step %.1f ms, SP sub-step %.1f ms, generator optimizer_step %.2f ms, D sub-step %.1f ms, "
+                  "discriminator optimizer_step %.2f ms (the batch's upload included in the sub-steps)"
+                  % (attn, Bb, TT, TM, med["ae"], med["sp"], med["opt_gen"], med["d"], med["opt_disc"]), flush=True)
+
+
+if a.train_step:
+    train_step_mode()
+    sys.exit(0)
 if a.train:
     train_mode()
     sys.exit(0)

@@ -5,7 +5,8 @@ Public surface kept:
   UNAST(text_m, speech_m, discriminator=None, teacher=None): text_ae, speech_ae, tts, asr, num_params
   TextTransformer / SpeechTransformer(args): encode, decode_sequence, forward, preprocess
   TextRNN / SpeechRNN(args): encode, decode, decode_sequence, infer_sequence, postprocess, forward -- eval mode under torch.no_grad() at the
-      full-size RNN configuration only (unast_amd.rnn; src/network.py:279-402, 503-624); training is not built
+      full-size RNN configuration only (unast_amd.rnn; src/network.py:279-402, 503-624); they train through unast_amd.train_rnn's tape entry
+      points, composed into the train step by unast_amd.train_rnn_step
   LSTMDiscriminator(d_in, hidden, out=1, bidirectional=False, num_layers=1, dropout=.2, relu=.2).forward(out, out_len)
   Discriminator(enc_dim, hidden=1024, out_classes=1, dropout=.2, relu=.2).forward(enc_output)
   Vocoder(num_mels, hidden_size, num_fft).forward(mel) -- eval mode under torch.no_grad() only (unast_amd.vocoder) -- and make_mags;
@@ -785,7 +786,13 @@ class UNAST(_Side):
         st = self.__dict__.get("_unast_store")
         dev = next(self.parameters()).device
         if st is None or st.device != dev:
-            st = FlatStore(self, prefix="")
+            if isinstance(self.text_m, _RNNModel):
+                # the RNN generators live in their optimizer's flat buffers (unast_amd.train_rnn_step); the store holds what reads it: the discriminator
+                if self.discriminator is None:
+                    raise RuntimeError("an RNN model without a discriminator has no parameter store (unast_amd.train_rnn_step)")
+                st = FlatStore(self.discriminator, prefix="discriminator.")
+            else:
+                st = FlatStore(self, prefix="")
             self.__dict__["_unast_store"] = st
         return st
 

@@ -7,6 +7,8 @@ Same function names, arguments, return values and `losses[...]` keys as the refe
   get_linear_schedule_with_warmup, get_transformer_paper_schedule, initialize_model, train_step (one outer step of
   train()'s hot loop, src/train.py:602-655).
 Module globals DEVICE and WRITER are set by the caller, as in the reference (src/train.py:1005-1012).
+With args.model_type == 'rnn' the entry points dispatch to unast_amd.train_rnn_step (explicit tape calls instead of autograd segments; the
+cross-model step is refused there).
 
 Differences that are deliberate and MI355X-motivated:
   * losses are fused HIP kernels (forward scalar + backward dlogits); `.item()` logging reads are deferred: the
@@ -330,8 +332,25 @@ def check_nan_loss(model, loss, loss_type, *unused):
 
 
 #####----- Use these to run a task on a batch ----#####
+def _is_rnn(args):
+    return getattr(args, "model_type", "transformer") == 'rnn'
+
+
+def _rnn_refuse_direct(args, name, step_name):
+    if _is_rnn(args):
+        from . import train_rnn_step
+        raise NotImplementedError(train_rnn_step.DIRECT_REASON % (name, step_name))
+
+
+def _rnn_refuse_cm(args):
+    if _is_rnn(args):
+        from . import train_rnn_step
+        raise NotImplementedError(train_rnn_step.CM_REASON)
+
+
 def autoencoder_step(model, batch, args, use_dis_loss=False):
     """src/train.py:199-229."""
+    _rnn_refuse_direct(args, "autoencoder_step", "train_ae_step")
     x, y = batch
     text, mel, text_len, mel_len = x
     gold_char, gold_mel, gold_stop = y
@@ -353,6 +372,7 @@ def autoencoder_step(model, batch, args, use_dis_loss=False):
 
 def supervised_step(model, batch, args, use_dis_loss=False):
     """src/train.py:231-259."""
+    _rnn_refuse_direct(args, "supervised_step", "train_sp_step")
     x, y = batch
     text, mel, text_len, mel_len = x
     gold_char, gold_mel, gold_stop = y
@@ -375,6 +395,7 @@ def supervised_step(model, batch, args, use_dis_loss=False):
 
 def crossmodel_step(model, batch, args, use_dis_loss=False):
     """src/train.py:261-294.  The two directions' generations are independent and run in lock-step (UNAST.cm_both_in)."""
+    _rnn_refuse_cm(args)
     x, y = batch
     text, mel, text_len, mel_len = x
     gold_char, gold_mel, gold_stop = y
@@ -397,9 +418,15 @@ def crossmodel_step(model, batch, args, use_dis_loss=False):
 @on_stream("disc")
 def discriminator_shuffle_batch(t_hid, t_hid_len, s_hid, s_hid_len, model_type, train_discriminator=False, out=None):
     """src/train.py:296-329 for model_type == 'transformer'.  out (not in the reference's signature): a [2B, Tmax, D] row block of a larger
-    buffer that receives the batch (train_gen_joint_step puts two sub-steps' batches side by side)."""
+    buffer that receives the batch (train_gen_joint_step puts two sub-steps' batches side by side).  model_type == 'rnn': (hidden, enc_output)
+    pairs in (`_, t_out = t_hid`), unast_amd.train_rnn_step."""
+    if model_type == 'rnn':
+        if out is not None:
+            raise NotImplementedError("discriminator_shuffle_batch(out=) serves the transformer family's joint generator step")
+        from . import train_rnn_step
+        return train_rnn_step.discriminator_shuffle_batch(t_hid, t_hid_len, s_hid, s_hid_len, train_discriminator)
     if model_type != 'transformer':
-        raise NotImplementedError("only the transformer family is on the MI355X path")
+        raise NotImplementedError("model_type must be 'transformer' or 'rnn'")
     B, Tt, Dm = t_hid.shape
     Ts = s_hid.shape[1]
     Tmax = max(Tt, Ts)
@@ -457,6 +484,9 @@ def discriminator_step(model, batch, args):
 #####---- Use these to train on a task -----#####
 def optimizer_step(model, optimizer, args, defer=False):
     """src/train.py:358-363: clip_grad_norm_ -> optimizer.step() -> zero_grad(set_to_none=True)."""
+    if _is_rnn(args):
+        from . import train_rnn_step
+        return train_rnn_step.optimizer_step(model, optimizer, args)
     if isinstance(optimizer, FusedAdamW):
         st = model._store()
         ds = stream_of("disc") if (defer and st.touched == {"disc"}) else None
@@ -481,6 +511,9 @@ def optimizer_step(model, optimizer, args, defer=False):
 
 def train_sp_step(losses, model, batch, step, accum_steps, args):
     """src/train.py:365-390."""
+    if _is_rnn(args):
+        from . import train_rnn_step
+        return train_rnn_step.train_sp_step(losses, model, batch, step, accum_steps, args)
     batch = process_batch(batch)
     with side_streams():                       # text side / speech side / discriminator on three HIP streams
         if args.use_discriminator:
@@ -500,6 +533,9 @@ def train_sp_step(losses, model, batch, step, accum_steps, args):
 
 def train_ae_step(losses, model, batch, step, accum_steps, args):
     """src/train.py:392-416."""
+    if _is_rnn(args):
+        from . import train_rnn_step
+        return train_rnn_step.train_ae_step(losses, model, batch, step, accum_steps, args)
     batch = process_batch(batch)
     with side_streams():
         if args.use_discriminator:
@@ -610,6 +646,8 @@ def joint_generator_phase(args, ae_batch, sp_batch):
     """Whether the generator phase of one outer step can run as train_gen_joint_step: one auto-encoder and one supervised sub-step, no
     cross-model sub-step between them, and the two batches in one shape."""
     from . import config
+    if _is_rnn(args):
+        return False
     if not config.JOINT_GEN or args.ae_steps != 1 or args.sp_steps != 1 or getattr(args, "cm_steps", 0) != 0:
         return False
     return all(tuple(a.shape) == tuple(b.shape) for a, b in zip(ae_batch[:2], sp_batch[:2]))
@@ -617,6 +655,7 @@ def joint_generator_phase(args, ae_batch, sp_batch):
 
 def train_cm_step(losses, model, batch, step, accum_steps, args):
     """src/train.py:418-444."""
+    _rnn_refuse_cm(args)
     batch = process_batch(batch)
     if args.use_discriminator:
         t_cm_loss, s_cm_loss, d_cm_loss = crossmodel_step(model, batch, args, args.use_discriminator)
@@ -636,6 +675,9 @@ def train_cm_step(losses, model, batch, step, accum_steps, args):
 def train_discriminator_step(losses, model, batch, step, accum_steps, args, log_out_to_tb=False, defer=False):
     """src/train.py:446-463.  `defer` (used by the training loop, not part of the reference signature): leave the D phase on
     the discriminator's stream instead of joining it into the caller's stream."""
+    if _is_rnn(args):
+        from . import train_rnn_step
+        return train_rnn_step.train_discriminator_step(losses, model, batch, step, accum_steps, args, log_out_to_tb)
     batch = process_batch(batch)
     with side_streams() as ctx:
         d_loss, d_output = discriminator_step(model, batch, args)
@@ -672,6 +714,8 @@ def train_step(losses, model, optimizer, scheduler, batches, step, args, defer_d
     defer_d_phase=True leaves the discriminator phase (backward, clip + AdamW) on its own HIP stream so that the NEXT call's
     generator forward overlaps it; the caller then has to `join_streams()` (or synchronise the device) before reading
     parameters, gradients or losses from its own stream.  train() does that at every epoch end."""
+    if _is_rnn(args) and getattr(args, "cm_steps", 0) > 0:
+        _rnn_refuse_cm(args)
     if not model.training:
         model.train()
     if args.use_discriminator:
@@ -727,6 +771,11 @@ def train(args, batch_getter=None, on_epoch_end=None, valid_dataloader=None):
     best-PER checkpointing run at each epoch end when `valid_dataloader` is given, src/train.py:668-679):
     per outer step ae_steps x AE, sp_steps x SP (accumulated, scaled by 1/accum_steps), optimizer_step, then d_steps x D,
     optimizer_step, scheduler.step().  Returns (model, per-epoch loss means)."""
+    if _is_rnn(args):
+        if getattr(args, "cm_steps", 0) > 0:
+            _rnn_refuse_cm(args)
+        if getattr(args, "use_hip_graphs", False) or valid_dataloader is not None:
+            raise NotImplementedError("model_type='rnn': graph capture of the loops and evaluate() are not built (unast_amd.train_rnn_step)")
     set_seed(args.seed)
     batch_getter = batch_getter or SyntheticBatchGetter(args)
     s_epoch, best, model, optimizer, scheduler = initialize_model(args)
@@ -1038,16 +1087,21 @@ def allreduce_grads(st, ranges, scale_fn=None):
 
 
 def initialize_model(args):
-    """src/train.py:910-959 for model_type == 'transformer'."""
-    if args.model_type != 'transformer':
-        raise NotImplementedError("only model_type='transformer' is on the MI355X path (SURVEY.md section 2, row 11)")
-    text_m, speech_m, discriminator, teacher = TextTransformer(args), SpeechTransformer(args), None, get_teacher_ratio(args)
-    if args.use_discriminator:
-        discriminator = LSTMDiscriminator(args.hidden, args.disc_hid, bidirectional=args.disc_bidirectional, num_layers=args.disc_num_layers)
-    model = UNAST(text_m, speech_m, discriminator, teacher).to(_dev())
-    if args.optim_type not in ('adam', 'adamw'):
-        raise ValueError("optim_type must be adam or adamw")
-    optimizer = FusedAdamW(model, lr=args.lr, weight_decay=args.weight_decay, decoupled=(args.optim_type == 'adamw'))
+    """src/train.py:910-959.  model_type == 'rnn': UNAST(TextRNN, SpeechRNN[, LSTMDiscriminator(2 * hidden, ..)]) and its RNNFlatAdamW
+    (unast_amd.train_rnn_step.build)."""
+    if args.model_type == 'rnn':
+        from . import train_rnn_step
+        model, optimizer = train_rnn_step.build(args, _dev())
+    elif args.model_type != 'transformer':
+        raise NotImplementedError("model_type must be 'transformer' or 'rnn'")
+    else:
+        text_m, speech_m, discriminator, teacher = TextTransformer(args), SpeechTransformer(args), None, get_teacher_ratio(args)
+        if args.use_discriminator:
+            discriminator = LSTMDiscriminator(args.hidden, args.disc_hid, bidirectional=args.disc_bidirectional, num_layers=args.disc_num_layers)
+        model = UNAST(text_m, speech_m, discriminator, teacher).to(_dev())
+        if args.optim_type not in ('adam', 'adamw'):
+            raise ValueError("optim_type must be adam or adamw")
+        optimizer = FusedAdamW(model, lr=args.lr, weight_decay=args.weight_decay, decoupled=(args.optim_type == 'adamw'))
     s_epoch, best = 0, 300
     if getattr(args, "load_path", None) is not None and os.path.isfile(args.load_path):
         from .checkpoint import load_ckp

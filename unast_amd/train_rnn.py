@@ -517,6 +517,7 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     outs = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)                                 # position 0 = the all-zero go frame
     outs[:, 1:].copy_(head[:, :, :M])
     tape.stop = head[:, :, M].contiguous()
+    tape.head = head                                                                        # [pre | stop | zero columns]: what the loss kernels read
     N1 = B * (T + 1)
     tape.xs, tape.zs = [outs.view(N1, M)], []
     tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
@@ -918,7 +919,8 @@ def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
         ops.leaky_dropout(o, None, o2, 1.0, p_post, seed, S_TPOST)
     tape.site("t_post_dropout", p_post, S_TPOST, N, 256)
     tape.o2 = o2
-    tape.logits = _linear_rows(o2, P.head[0], P.head[1]).view(B, T, P.ldh)[:, :, :P.V].contiguous()
+    tape.head = _linear_rows(o2, P.head[0], P.head[1])                                      # [N, ldh] padded logits: what the loss kernels read
+    tape.logits = tape.head.view(B, T, P.ldh)[:, :, :P.V].contiguous()
     return tape
 
 

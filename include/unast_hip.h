@@ -378,6 +378,40 @@ int unast_prefix_embed_fwd(const int64_t* target, const float* E, const int* chu
                            int vocab, int sos, float* out, float drop_p, unsigned int seed, unsigned int stream_id, hipStream_t stream);
 int unast_prefix_embed_bwd(const float* dx, const int* segoff, int slab_rows, int B, int T, int C, float* G, float drop_p, unsigned int seed,
                            unsigned int stream_id, hipStream_t stream);
+/* The single-prefix prenet of TextRNN's greedy generation in TRAIN mode (csrc/prefix_gen.hip): TextRNN.infer_sequence under
+ * UNAST.cm_speech_in (src/network.py:114-123, 586-617) calls TextPrenet (src/module.py:217-230) on the whole prefix [SOS, c_0 .. c_{L-2}] at every
+ * position -- a [B, L, 256] batch with fresh dropout masks, batch statistics over its B*L rows and one momentum update.  Rows are b*L + j; the
+ * dropout masks' row is row0 + (b*L + j).  2 <= B, B*L <= 2^20.  No atomics, no workgroup waits on another; rows past B*L are never read.
+ * unast_prefix_gen_tiles: the number of 32-row tiles of a prefix = the leading dimension of a stage's partial sums [tiles][2][256] (doubles).
+ * unast_prefix_gen_conv: one prenet stage: z [B*L,256] = conv5_same(input) + bias on v_mfma_f32_16x16x4_f32, every sequence zero-padded on its own, and
+ *   part_out = per-tile fp64 sums of z and z^2.  The input rows are made by the loader.  Stage 1 (tokens given, x null): dropout(emb[id]), id = sos at
+ *   j = 0 and tokens[b*ld_tok + j - 1] after that (int64; an id outside the table gives a zero row; tokens at or past L - 1 are not read), Cin = emb
+ *   width (a multiple of 64, at most 256), W [256,5,Cin] tap-major.  Stages 2, 3 (x given, tokens null): dropout(relu(batchnorm(x))) with the
+ *   statistics of x reduced in tile order from part_in, gamma / beta / eps of that BatchNorm, Cin = 256.
+ * unast_prefix_gen_finish: pre [B, ldp >= 256] = dropout(relu(batchnorm(z3))) of each sequence's LAST row (statistics over all B*L rows, from
+ *   part = the three stages' partial sums [3][tiles][2][256]); then, only while *running != 0 (running null = always): the momentum update of
+ *   the three BatchNorms' running statistics (unbiased variance, n = B*L; a null pair is skipped) and num_batches_tracked += 1 each.
+ * unast_prefix_gen_act_drop: out = dropout_b(dropout_a(act(x))) over [B,C] rows (act 0 none, 1 tanh, 2 relu): RNNDecoder's tanh + dropout1 and
+ *   TextPostnet.dropout1 (src/module.py:373-375, 242-246) or SpeechPrenet's relu + dropout (src/module.py:95-110) of one generated position; the
+ *   masks' row is row0 + b.
+ * unast_prefix_gen_end_text / _end_speech: the end of a generated position (src/network.py:601-609 / 326-337), one workgroup, everything only
+ *   while *running != 0: text: tokens[b*ld_tok + pos] = first maximum of logits[b, 0..V); speech: frames[b, pos + 1, 0..M) = head[b, 0..M),
+ *   stops[b*ld_stop + pos] = head[b, M]; a sequence whose stop_lens is still max_len and that draws eos / sigmoid(stop) >= .5 gets
+ *   stop_lens = pos + 1; running = some stop_lens is still max_len. */
+int unast_prefix_gen_tiles(int B, int L);
+int unast_prefix_gen_conv(const float* x, const double* part_in, const float* gamma, const float* beta, float eps, const int64_t* tokens, int ld_tok,
+                          const float* emb, int vocab, int sos, const float* W, const float* bias, float* z, double* part_out, int B, int L, int Cin,
+                          float drop_p, unsigned int seed, unsigned int stream_id, unsigned int row0, hipStream_t stream);
+int unast_prefix_gen_finish(const float* z3, const double* part, const float* gamma, const float* beta, float eps, float* pre, int ldp,
+                            float* rm1, float* rv1, int64_t* nbt1, float mom1, float* rm2, float* rv2, int64_t* nbt2, float mom2,
+                            float* rm3, float* rv3, int64_t* nbt3, float mom3, const int* running, int B, int L, float drop_p, unsigned int seed,
+                            unsigned int stream_id, unsigned int row0, hipStream_t stream);
+int unast_prefix_gen_act_drop(const float* x, int ldx, float* out, int ldo, int B, int C, int act, float drop_a, unsigned int stream_a, float drop_b,
+                              unsigned int stream_b, unsigned int seed, unsigned int row0, hipStream_t stream);
+int unast_prefix_gen_end_text(const float* logits, int ld, int V, int B, int64_t* tokens, int ld_tok, int pos, int64_t* stop_lens, int64_t max_len,
+                              int eos, int* running, hipStream_t stream);
+int unast_prefix_gen_end_speech(const float* head, int ld, int M, int B, float* frames, int ld_fr, float* stops, int ld_stop, int pos,
+                                int64_t* stop_lens, int64_t max_len, int* running, hipStream_t stream);
 /* TextRNN.decode's prenet input (src/network.py:573 runs TextPrenet over the whole prefix and keeps its last position, which depends on the
  * prefix's last 7 tokens): out [B,W,E] = embedding rows of prefix positions p-W+1 .. p, zero rows for positions before the prefix.  The prefix at
  * device position *pos is tokens[b, 0..*pos] (generation, src/network.py:590-600; p = *pos) or, teacher_forced, [sos] at *pos = 0 and

@@ -13,7 +13,14 @@ saved bytes, and the prefix prenet issued position by position through the unifo
 --train-step: the whole train step of the family (unast_amd.train_rnn_step through unast_amd.train's entry points, dropout, noise, SpecAugment
 and the drawn permutation on) at T_text = 180, T_mel = 800, B in {4, 16}, both attention types -- ms per AE / SP / D sub-step and per
 optimizer step of each phase, one warm-up round and medians of 5.
-Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder | --train-step]"""
+--train-cm: the cross-model sub-step (unast_amd.train_rnn_step.train_cm_step) at T_text = 180, T_mel = 800, B in {4, 16}, both attention
+types, dropout on, one warm-up and medians of 5.  Generation length depends on the weights, so the stop rule is OFF here (the EOS and stop
+biases are set so that no sequence stops) and both generations run a fixed position count: 180 text positions, 800 frames.  Reports the text
+prenet per position, fused (csrc/prefix_gen.hip: 4 launches) against the comparator composed from the uniform-[B,L] entry points (unast_embed_fwd,
+the three-launch conv with its operand split, train-mode unast_bn_fwd: 23 device operations), averaged over the prefixes L = 1..180, and the
+fused form at single prefix lengths L = 1 / 60 / 180 / 300 (its loaders reduce every tile's partial sums again: O(tiles^2) per launch); text and
+speech generation per position; and the whole sub-step.
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder | --train-step | --train-cm]"""
 import argparse
 import os
 import statistics
@@ -35,6 +42,7 @@ ap.add_argument("--train", action="store_true")
 ap.add_argument("--train-decoder", action="store_true")
 ap.add_argument("--train-text-decoder", action="store_true")
 ap.add_argument("--train-step", action="store_true")
+ap.add_argument("--train-cm", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -304,6 +312,113 @@ def train_step_mode():
                   % (attn, Bb, TT, TM, med["ae"], med["sp"], med["opt_gen"], med["d"], med["opt_disc"]), flush=True)
 
 
+def train_cm_mode():
+    import json
+    from collections import defaultdict
+    from types import SimpleNamespace
+    from unast_amd import train, train_rnn, train_rnn_step
+    from unast_amd.rnn import _conv
+    from unast_amd.utils import SOS_IDX, EOS_IDX
+    train.DEVICE = D
+    cfgs = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "rnn_configs.json")))
+    train_rnn_step.TEXT_MAX_LEN, train_rnn_step.SPEECH_MAX_LEN = TT, TM
+    for attn in ("luong", "lsa"):
+        for Bb in (4, 16):
+            args = SimpleNamespace(**dict(cfgs["rnn_d_" + attn], load_path=None, ae_steps=1, sp_steps=1, cm_steps=1, d_steps=1, train_batch_size=Bb))
+            train.set_seed(0)
+            _, _, model, opt, _ = train.initialize_model(args)
+            model.train()
+            tm, sm = model.text_m, model.speech_m
+            with torch.no_grad():                                                                 # the stop rule off: a fixed position count
+                tm.postnet.fc1.bias[EOS_IDX] = -1e4
+                sm.postnet.stop_linear.bias.fill_(-30.0)
+            train_rnn_step.drop_cached_operands(model)
+            if attn == "luong":
+                # ---- the text prenet of one position, averaged over the prefixes L = 1..TT: fused against the comparator
+                P = train_rnn.decoder_pack_of(tm, train_rnn.TextDecoderPack)
+                bns = [bn for _, _, _, bn in P.convs]
+                p = float(tm.prenet.p)
+                LMAX = max(TT, 300)                                                               # (300 = infer_sequence's max_len: the longest prefix)
+                tokens = torch.randint(3, 46, (Bb, LMAX), device=D)
+                ids_sos = torch.cat([torch.full((Bb, 1), SOS_IDX, dtype=torch.int64, device=D), tokens], 1)
+                zs = [torch.empty(Bb * LMAX, 256, device=D) for _ in range(3)]
+                parts = torch.empty(3 * ops.prefix_gen_tiles(Bb, LMAX) * 512, dtype=torch.float64, device=D)
+                pre = torch.empty(Bb, 256, device=D)
+
+                def fused_at(L):
+                    row0 = train_rnn.prefix_row0(Bb, L)
+                    part = parts[:3 * ops.prefix_gen_tiles(Bb, L) * 512].view(3, -1, 2, 256)
+                    ops.prefix_gen_conv(P.convs[0][0][0], P.convs[0][1], zs[0], part[0], Bb, L, tokens=tokens, emb=P.emb, sos=SOS_IDX, drop_p=p, seed=1,
+                                        stream_id=21, row0=row0)
+                    for k in (1, 2):
+                        bn = bns[k - 1]
+                        ops.prefix_gen_conv(P.convs[k][0][0], P.convs[k][1], zs[k], part[k], Bb, L, x=zs[k - 1], part_in=part[k - 1],
+                                            bn=(bn.weight, bn.bias, bn.eps), drop_p=p, seed=1, stream_id=21 + k, row0=row0)
+                    ops.prefix_gen_finish(zs[2], part, bns, pre, Bb, L, drop_p=p, seed=1, stream_id=24, row0=row0)
+
+                def fused():
+                    for L in range(1, TT + 1):
+                        fused_at(L)
+
+                mean, rstd, bn_ws = torch.empty(256, device=D), torch.empty(256, device=D), torch.empty(512, dtype=torch.float64, device=D)
+
+                def comparator():
+                    for L in range(1, TT + 1):
+                        ids = ids_sos[:, :L].contiguous()
+                        N = Bb * L
+                        x = torch.empty(N, P.emb.shape[1], device=D)
+                        ops.embed_fwd(ids, P.emb, x, L, drop_p=p, seed=1, stream_id=21)
+                        cur = x.view(Bb, L, -1)
+                        for k, (wp, bias, _, bn) in enumerate(P.convs):
+                            z = _conv(cur, wp, bias, 2)
+                            y = torch.empty(N, 256, device=D)
+                            ops.bn_fwd(z.view(N, 256), bn.weight, bn.bias, y, mean, rstd, bn.running_mean, bn.running_var, bn_ws, 1, drop_p=p, seed=1,
+                                       stream_id=22 + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
+                            cur = y.view(Bb, L, 256)
+                        pre.copy_(cur[:, -1])
+                with torch.no_grad():
+                    f_ms, c_ms = median_ms(fused, reps=5), median_ms(comparator, reps=5)
+                print("text prenet of one position, B=%d, mean over L = 1..%d: fused %.1f us (4 launches), comparator %.1f us (23 device operations + the "
+                      "last-row copy) -> x %.2f" % (Bb, TT, f_ms * 1e3 / TT, c_ms * 1e3 / TT, c_ms / f_ms), flush=True)
+                # every workgroup of stages 2 and 3 reduces all the tiles' partial sums again (O(tiles^2) per launch): the cost by prefix length
+                with torch.no_grad():
+                    per_l = [(L, median_ms(lambda: [fused_at(L) for _ in range(20)], reps=5) * 1e3 / 20) for L in (1, 60, 180, 300)]
+                print("fused text prenet of one position by prefix length, B=%d: %s" % (Bb, ", ".join("L = %d (%d tiles) %.1f us" % (L, ops.prefix_gen_tiles(Bb, L), us)
+                                                                                                   for L, us in per_l)), flush=True)
+            # ---- the two generations, fixed position count
+            getter = train.SyntheticBatchGetter(args, t_text=TT, t_mel=TM)
+            text, mel, tl, ml = train_rnn_step._process(getter._next())[:4]
+            with torch.no_grad():
+                s_mem = train_rnn.encoder_forward(sm, mel, ml, seed=1)
+                t_mem = train_rnn.encoder_forward(tm, text, tl, seed=2)
+                got = []
+                gt_ms = median_ms(lambda: got.append(train_rnn.text_generate_train(tm, s_mem, ml, max_len=TT, seed=3)), reps=5)
+                assert got[-1].lens_host == [TT] * Bb, got[-1].lens_host
+                gs_ms = median_ms(lambda: got.append(train_rnn.speech_generate_train(sm, t_mem, tl, max_len=TM, seed=4)), reps=5)
+                assert got[-1].lens_host == [TM] * Bb, got[-1].lens_host
+            print("[%s] B=%d dropout on, stop rule off: text generation %d positions over a %d-frame memory %.1f ms = %.1f us per position (16 launches); "
+                  "speech generation %d frames over a %d-token memory %.1f ms = %.1f us per position (15 launches; the post-net after the loop included)"
+                  % (attn, Bb, TT, TM, gt_ms, gt_ms * 1e3 / TT, TM, TT, gs_ms, gs_ms * 1e3 / TM), flush=True)
+            # ---- the whole sub-step
+            times, losses = [], defaultdict(list)
+            train.freeze_model_parameters(model.discriminator)
+            for rep in range(6):                                                                  # one warm-up round, five measured
+                b = getter._next()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                train_rnn_step.train_cm_step(losses, model, b, 0, 3, args)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+                train_rnn_step.optimizer_step(model, opt, args)
+            assert all(bool(torch.isfinite(torch.as_tensor(v))) for vs in losses.values() for v in vs)
+            print("[%s] B=%d T_text=%d T_mel=%d: CM sub-step %.1f ms (generated: %d tokens, %d frames; live PAD ids %d)"
+                  % (attn, Bb, TT, TM, statistics.median(times[1:]), TT, TM, model._rnn_cm_live_pad), flush=True)
+
+
+if a.train_cm:
+    train_cm_mode()
+    sys.exit(0)
 if a.train_step:
     train_step_mode()
     sys.exit(0)

@@ -611,6 +611,132 @@ def prefix_embed_bwd(dx, lay, G, drop_p=0.0, seed=0, stream_id=0):
           "unast_prefix_embed_bwd")
 
 
+# ---- the single-prefix prenet and the position ends of train-mode generation (csrc/prefix_gen.hip) ----------------------------------------------
+def prefix_gen_tiles(B, L):
+    return lib().unast_prefix_gen_tiles(B, L)
+
+
+def _pgen_rows(name, B, L, *named):
+    if B < 2 or L < 1:
+        raise ValueError("%s: 2 <= B, 1 <= L (got B = %d, L = %d)" % (name, B, L))
+    for t, n, cols in named:
+        _f32(t, n)
+        if t.dim() != 2 or t.shape[0] < B * L or t.shape[1] != cols or not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous [>= B*L = %d, %d] (got %s)" % (name, n, B * L, cols, tuple(t.shape)))
+
+
+def _pgen_part(name, part, tiles, lead=()):
+    if not (part.is_cuda and part.dtype is torch.float64 and part.is_contiguous() and part.dim() == len(lead) + 3 and tuple(part.shape[:len(lead)]) == lead and
+            part.shape[len(lead)] >= tiles and tuple(part.shape[len(lead) + 1:]) == (2, 256)):
+        raise ValueError("%s: partial sums must be contiguous float64 %s[>= %d tiles, 2, 256] (got %s)" % (name, list(lead), tiles, tuple(part.shape)))
+
+
+def prefix_gen_conv(Wp, bias, z, part_out, B, L, x=None, part_in=None, bn=None, tokens=None, emb=None, sos=0, drop_p=0.0, seed=0, stream_id=0, row0=0):
+    """One prenet stage over the prefix [B, L]: z[:B*L] [.,256] = conv5(input) + bias, part_out [tiles,2,256] its column sums.  Wp [256,5,Cin]
+    tap-major.  Stage 1: tokens int64 [B, ld] (the generated tokens; SOS is implied at row 0) and emb [V,Cin]; stages 2, 3: x = the previous
+    stage's z, part_in its sums, bn = (gamma, beta, eps).  The dropout (on the input rows) draws row row0 + b*L + j."""
+    tiles = prefix_gen_tiles(B, L)
+    _pgen_rows("prefix_gen_conv", B, L, (z, "z", 256))
+    _pgen_part("prefix_gen_conv", part_out, tiles)
+    _f32(Wp, "Wp"), _f32(bias, "bias")
+    if Wp.dim() != 3 or Wp.shape[0] != 256 or Wp.shape[1] != 5 or not Wp.is_contiguous() or bias.numel() != 256:
+        raise ValueError("prefix_gen_conv: Wp contiguous [256,5,Cin], bias [256]")
+    Cin = Wp.shape[2]
+    if (x is None) == (tokens is None):
+        raise ValueError("prefix_gen_conv: give x, part_in and bn (stages 2, 3) or tokens and emb (stage 1)")
+    if x is not None:
+        _pgen_rows("prefix_gen_conv", B, L, (x, "x", 256))
+        _pgen_part("prefix_gen_conv", part_in, tiles)
+        gamma, beta, eps = bn
+        _f32(gamma, "gamma"), _f32(beta, "beta")
+        if Cin != 256 or gamma.numel() != 256 or beta.numel() != 256:
+            raise ValueError("prefix_gen_conv: stages 2 and 3 run 256 channels in")
+        args = (_p(x), _p(part_in), _p(gamma), _p(beta), float(eps), None, 0, None, 0, 0)
+    else:
+        _f32(emb, "emb")
+        if not (tokens.is_cuda and tokens.dtype is torch.int64 and tokens.dim() == 2 and tokens.shape[0] == B and tokens.stride(1) == 1 and
+                tokens.shape[1] >= L - 1):
+            raise ValueError("prefix_gen_conv: tokens must be an int64 CUDA tensor [B, >= L - 1] with unit column stride")
+        if emb.dim() != 2 or emb.shape[1] != Cin or not emb.is_contiguous():
+            raise ValueError("prefix_gen_conv: emb contiguous [V, Cin = %d]" % Cin)
+        args = (None, None, None, None, 0.0, _p(tokens), tokens.stride(0), _p(emb), emb.shape[0], sos)
+    check(lib().unast_prefix_gen_conv(*args, _p(Wp), _p(bias), _p(z), _p(part_out), B, L, Cin, drop_p, seed & 0xFFFFFFFF, stream_id, row0, _stream()),
+          "unast_prefix_gen_conv")
+    return z
+
+
+def prefix_gen_finish(z3, part, bns, pre, B, L, running=None, drop_p=0.0, seed=0, stream_id=0, row0=0):
+    """pre [B, 256] = dropout(relu(batchnorm3(z3))) of each sequence's last row; part [3, tiles, 2, 256] = the three stages' sums; bns = the three
+    BatchNorm1d modules.  While running (an int32 CUDA scalar, None = always) is non-zero their running statistics take one momentum update and
+    num_batches_tracked += 1."""
+    tiles = prefix_gen_tiles(B, L)
+    _pgen_rows("prefix_gen_finish", B, L, (z3, "z3", 256))
+    _pgen_part("prefix_gen_finish", part, tiles, lead=(3,))
+    if part.shape[1] != tiles:
+        raise ValueError("prefix_gen_finish: part must be [3, tiles = %d, 2, 256] exactly (the stages' sums lie tiles*512 doubles apart)" % tiles)
+    ldp = _rows(pre, "pre", B, 256)
+    if running is not None and not (running.is_cuda and running.dtype is torch.int32 and running.numel() == 1):
+        raise ValueError("prefix_gen_finish: running must be an int32 CUDA scalar")
+    if len(bns) != 3:
+        raise ValueError("prefix_gen_finish: three BatchNorm1d modules")
+    stats = []
+    for bn in bns:
+        stats += [_p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), float(bn.momentum)]
+    b3 = bns[2]
+    check(lib().unast_prefix_gen_finish(_p(z3), _p(part), _p(b3.weight), _p(b3.bias), float(b3.eps), _p(pre), ldp, *stats, _p(running), B, L, drop_p,
+                                        seed & 0xFFFFFFFF, stream_id, row0, _stream()), "unast_prefix_gen_finish")
+    return pre
+
+
+PGEN_NONE, PGEN_TANH, PGEN_RELU = 0, 1, 2
+
+
+def prefix_gen_act_drop(x, out, act, drop_a=0.0, stream_a=0, drop_b=0.0, stream_b=0, seed=0, row0=0):
+    """out = dropout_b(dropout_a(act(x))) over [B, C] rows; the masks' row is row0 + b."""
+    B, C = x.shape
+    ldx, ldo = _rows(x, "x", B, C), _rows(out, "out", B, C)
+    check(lib().unast_prefix_gen_act_drop(_p(x), ldx, _p(out), ldo, B, C, act, drop_a, stream_a, drop_b, stream_b, seed & 0xFFFFFFFF, row0, _stream()),
+          "unast_prefix_gen_act_drop")
+    return out
+
+
+def _pgen_state(name, stop_lens, running, B):
+    if not (stop_lens.is_cuda and stop_lens.dtype is torch.int64 and stop_lens.is_contiguous() and stop_lens.numel() == B):
+        raise ValueError("%s: stop_lens must be a contiguous int64 CUDA tensor [B]" % name)
+    if not (running.is_cuda and running.dtype is torch.int32 and running.numel() == 1):
+        raise ValueError("%s: running must be an int32 CUDA scalar" % name)
+
+
+def _pgen_wide(name, t, what, cols):
+    _f32(t, what)
+    if t.dim() != 2 or t.shape[1] < cols or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError("%s: %s must be [B, >= %d] with unit column stride (got %s)" % (name, what, cols, tuple(t.shape)))
+    return t.stride(0)
+
+
+def prefix_gen_end_text(logits, V, tokens, pos, stop_lens, max_len, eos, running):
+    """The end of text position pos, under the running flag: tokens[:, pos] = argmax(logits[:, :V]), first EOS -> stop_lens = pos + 1, running."""
+    B = logits.shape[0]
+    ld = _pgen_wide("prefix_gen_end_text", logits, "logits", V)
+    _pgen_state("prefix_gen_end_text", stop_lens, running, B)
+    if not (tokens.is_cuda and tokens.dtype is torch.int64 and tokens.dim() == 2 and tokens.shape[0] == B and tokens.stride(1) == 1 and tokens.shape[1] >= max_len):
+        raise ValueError("prefix_gen_end_text: tokens must be an int64 CUDA tensor [B, >= max_len] with unit column stride")
+    check(lib().unast_prefix_gen_end_text(_p(logits), ld, V, B, _p(tokens), tokens.stride(0), pos, _p(stop_lens), max_len, eos, _p(running), _stream()),
+          "unast_prefix_gen_end_text")
+
+
+def prefix_gen_end_speech(head, M, frames, stops, pos, stop_lens, max_len, running):
+    """The end of speech position pos, under the running flag: frames[:, pos + 1] = head[:, :M], stops[:, pos] = head[:, M], the stop rule."""
+    B = head.shape[0]
+    ld = _pgen_wide("prefix_gen_end_speech", head, "head", M + 1)
+    _pgen_state("prefix_gen_end_speech", stop_lens, running, B)
+    _f32(frames, "frames"), _f32(stops, "stops")
+    if tuple(frames.shape) != (B, max_len + 1, M) or not frames.is_contiguous() or tuple(stops.shape) != (B, max_len) or not stops.is_contiguous():
+        raise ValueError("prefix_gen_end_speech: frames contiguous [B, max_len + 1, M], stops contiguous [B, max_len]")
+    check(lib().unast_prefix_gen_end_speech(_p(head), ld, M, B, _p(frames), frames.stride(0), _p(stops), stops.stride(0), pos, _p(stop_lens), max_len,
+                                            _p(running), _stream()), "unast_prefix_gen_end_speech")
+
+
 def posenc_fwd(x2d, pe, y, T, scale, drop_p=0.0, seed=0, stream_id=0):
     rows, D = x2d.shape
     check(lib().unast_posenc_fwd(_p(x2d), _p(pe), _p(y), rows, T, D, scale, drop_p, seed & 0xFFFFFFFF, stream_id, _stream()), "unast_posenc_fwd")

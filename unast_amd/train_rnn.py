@@ -25,6 +25,12 @@ TextRNN's decoder trains through the last pair (the end of this file)
 
     tape = text_decoder_forward(model, target, enc_outputs, lens_k, seed=0) # tape.logits [B,T,len(symbols)], tape.sites
     d_enc_output, d_h, d_c = text_decoder_backward(tape, d_logits)          # writes p.grad of model.prenet, model.decoder, model.postnet
+
+Greedy generation in TRAIN mode -- infer_sequence as UNAST.cm_speech_in / cm_text_in run it under no_grad with the modules in train() -- is the
+last section; no backward, no tape:
+
+    tokens, lens = text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0)
+    pre, post, stop, lens = speech_generate_train(model, enc_outputs, lens_k, max_len=815, seed=0)
 """
 import collections
 
@@ -518,26 +524,38 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     outs[:, 1:].copy_(head[:, :, :M])
     tape.stop = head[:, :, M].contiguous()
     tape.head = head                                                                        # [pre | stop | zero columns]: what the loss kernels read
-    N1 = B * (T + 1)
+    post = _postnet_forward(tape, outs, S_POST, "decoder_forward")
+    tape.pre, tape.post = outs[:, 1:], post[:, 1:]
+    return tape
+
+
+def _postnet_forward(tape, outs, stream0, what):
+    """SpeechPostnet in train mode over outs [B, T+1, M] (the go frame included, as the reference runs it): four conv + BatchNorm (batch
+    statistics over all B (T+1) rows, running statistics updated) + tanh + dropout stages and conv2, plus the residual.  Leaves the stages'
+    inputs and statistics on the tape (xs, zs, mean, rstd: what decoder_backward reads) and returns outs + postnet(outs) [B, T+1, M].
+    Shared by decoder_forward and speech_generate_train; stream0 = the first of the four dropout sites' stream ids."""
+    model, P, seed = tape.model, tape.P, tape.seed
+    B, T1, M = outs.shape
+    N1, dev = B * T1, outs.device
+    p_post = float(model.postnet.p)
     tape.xs, tape.zs = [outs.view(N1, M)], []
     tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
     bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
     cur = outs
     for k, (wp, bias, _, bn) in enumerate(P.post):
-        _check_bn(bn, "decoder_forward")
+        _check_bn(bn, what)
         z = _conv(cur, wp, bias, 4).view(N1, 256)
         y = _buf(N1, 256, dev=dev)
         ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, 2, drop_p=p_post, seed=seed,
-                   stream_id=S_POST + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
-        tape.site("post_dropout%d" % k, p_post, S_POST + k, N1, 256)
+                   stream_id=stream0 + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
+        tape.site("post_dropout%d" % k, p_post, stream0 + k, N1, 256)
         tape.zs.append(z)
         tape.xs.append(y)
-        cur = y.view(B, T + 1, 256)
+        cur = y.view(B, T1, 256)
     post = _conv(cur, P.post_out[0], P.post_out[1], 4)
     ops.add_inplace(post, outs)
     model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
-    tape.pre, tape.post = outs[:, 1:], post[:, 1:]
-    return tape
+    return post
 
 
 def _check_bn(bn, what):
@@ -979,3 +997,198 @@ def text_decoder_backward(tape, d_logits, accumulate=False, mark=None):
     if mark is not None:
         mark("prefix_end")
     return d_enc, d_h, d_c
+
+
+# ==== greedy generation in TRAIN mode: infer_sequence under UNAST.cm_speech_in / cm_text_in (src/network.py:103-123, 312-349, 586-617); DESIGN 5m =========
+# The modules are in train() under no_grad, so every dropout is live inside the decoding loop, TextPrenet normalises each generated prefix
+# [SOS, c_0 .. c_{i-1}] with that prefix's own batch statistics (one momentum update per position), and the speech post-net runs on batch
+# statistics over all generated frames.  No backward, no tape: the per-position buffers are scratch.  The loop is eager; the host knows the
+# position and reads the device-side `running` flag back every SYNC_EVERY positions.  Positions launched after every sequence has stopped write
+# neither tokens, frames, lengths, running statistics nor num_batches_tracked (the flag gates them on the device), so the results do not depend
+# on SYNC_EVERY.  Mask sites 21..34; a site's mask row is (position, sequence): i * B + b for the [B,256] rows of a position, and
+# B * L (L - 1) / 2 + b * L + j for row j of sequence b's prefix of length L = i + 1 (the rows of all shorter prefixes come first).
+SYNC_EVERY = 8
+S_GEMB, S_GPRE, S_GDROP, S_GOUT, S_GPOST = 21, 22, 25, 26, 27          # text: emb_dropout, dropout1..3 (22..24), nn.LSTM inter-layer, dropout1, TextPostnet.dropout1
+S_SGPRE, S_SGDROP, S_SGOUT, S_SGPOST = 28, 29, 30, 31                  # speech: prenet dropout, nn.LSTM inter-layer, dropout1, the four post-net dropouts (31..34)
+
+
+class Generated(tuple):
+    """What a train-mode generation returns: the reference's tuple, plus .lens_host (list), .steps (positions the host launched), .sites (the mask
+    sites, as a tape lists them), .max_len and -- text -- .live_pad (PAD ids inside a sequence's length)."""
+
+
+def prefix_row0(B, L):
+    """The first mask row of the prefix of length L: the rows of the prefixes of lengths 1 .. L-1 come before it."""
+    return B * (L * (L - 1) // 2)
+
+
+class _GenState:
+    """The position loop's scratch, shared by both generations: the attention state and the two LSTM cells, each ping-ponged between positions."""
+
+    def __init__(self, tape, max_len, stream_drop):
+        P, B, Tk, dev = tape.P, tape.B, tape.Tk, tape.enc.device
+        self.tape, self.lsa = tape, P.mode == ops.ATTN_LSA
+        Tkp = (Tk + 3) // 4 * 4
+        z = lambda *s: torch.zeros(*s, dtype=_F32, device=dev)                              # noqa: E731
+        self.mem = _linear_rows(tape.enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, P.A)
+        self.W, self.CUM = z(2, B, Tkp), (z(2, B, Tkp) if self.lsa else None)
+        self.HC, self.H0, self.H0d = z(2, B, 768), z(2, B, 256), _buf(B, 256, dev=dev)
+        self.S0, self.S1 = z(2, B, 5, 256), z(2, B, 5, 256)
+        self.H0[0].copy_(tape.h0[0])
+        self.xp0, self.ga, self.gb, self.tz, self.o = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev), _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+        self.p_dec = float(tape.model.decoder.p)
+        self.F1 = _drop_factor(self.p_dec, tape.seed, stream_drop, max_len * B, 256, dev).view(max_len, B, 256) if self.p_dec > 0.0 else None
+        tape.site("g_drop0", self.p_dec, stream_drop, max_len * B, 256)
+        self.stop_lens = torch.full((B,), max_len, dtype=torch.int64, device=dev)
+        self.running = torch.ones((), dtype=torch.int32, device=dev)
+
+    def step(self, i, pre):
+        """RNNDecoder on position i from the prenet's rows pre [B,256] up to the projection (the train-mode step of _loop_forward, 8 launches);
+        leaves [h1 | ctx] in HC[i & 1] and returns the projection's pre-activation [B,256]."""
+        t, P = self.tape, self.tape.P
+        Tk, cur, prv = t.Tk, i & 1, (i & 1) ^ 1
+        HC, H0, S0, S1, ga, gb = self.HC, self.H0, self.S0, self.S1, self.ga, self.gb
+        b_ih0, b_hh0, b_ih1, b_hh1 = P.bias
+        ops.rnn_linear(pre, P.w_ih0_p[0], b_ih0, self.xp0)
+        q = HC[prv, :, :256] if i else t.h0[1]                                              # the top layer's h from BEFORE this position's LSTM
+        ops.rnn_attn_step_train(P.mode, q, P.Wq, self.mem, P.v, t.enc, t.lens, HC[cur, :, 256:], self.W[cur, :, :Tk], prev_in=self.W[prv, :, :Tk],
+                                cum_in=self.CUM[prv, :, :Tk] if self.lsa else None, cum_out=self.CUM[cur, :, :Tk] if self.lsa else None, conv_w=P.conv_w,
+                                dense_w=P.dense_w)
+        ops.rnn_linear(HC[cur, :, 256:], P.w_ih0_c, None, gb, R=self.xp0)
+        ops.rnn_linear(H0[cur], P.w_hh0, b_hh0, ga, R=gb)                                   # H0[i & 1] = layer 0's h before position i
+        F1 = self.F1
+        h0_new = H0[prv]
+        ops.lstm_cell_train(ga, S0[prv, :, 4] if i else t.c0[0], S0[cur], h0_new, mask=F1[i] if F1 is not None else None, hd=self.H0d if F1 is not None else None)
+        ops.rnn_linear(self.H0d if F1 is not None else h0_new, P.w_ih1, b_ih1, gb)
+        ops.rnn_linear(q, P.w_hh1, b_hh1, ga, R=gb)
+        ops.lstm_cell_train(ga, S1[prv, :, 4] if i else t.c0[1], S1[cur], HC[cur, :, :256])
+        return ops.rnn_linear(HC[cur], P.proj[0][0], P.proj[1], self.tz)
+
+
+def _begin_generation(what, model, cls, pack_cls, enc_outputs, lens_k, max_len, seed):
+    if not isinstance(model, cls):
+        raise TypeError("%s: model must be a unast_amd.network.%s" % (what, cls.__name__))
+    if not model.training:
+        raise RuntimeError("%s generates in train mode (dropout and batch statistics live): call model.train() first (model.infer_sequence() is the "
+                           "eval generation)" % what)
+    max_len = int(max_len)
+    if not 1 <= max_len <= 2048:
+        raise ValueError("%s: 1 <= max_len <= 2048 (got %d)" % (what, max_len))
+    enc = enc_outputs.enc_output if isinstance(enc_outputs, Tape) else enc_outputs[1]
+    if not torch.is_tensor(enc) or enc.dim() != 3:
+        raise ValueError("%s: enc_outputs must be ((h, c), enc_output [B,Tk,512]) or an encoder tape" % what)
+    B = enc.shape[0]
+    if B < 2:
+        raise ValueError("%s: B >= 2 -- position 0 normalises B rows with batch statistics, one row cannot be normalised "
+                         "(the reference raises 'Expected more than 1 value per channel')" % what)
+    return _begin_decoder_tape(what, model, pack_cls, enc_outputs, lens_k, B, max_len, seed, enc.device), B, max_len
+
+
+def _run_positions(st, max_len, one):
+    """one(i) launches position i; the running flag is read back every SYNC_EVERY positions.  Returns the number of positions launched."""
+    steps = 0
+    for i in range(max_len):
+        one(i)
+        steps = i + 1
+        if steps % SYNC_EVERY == 0 and steps < max_len and not int(st.running.item()):
+            break
+    return steps
+
+
+@torch.no_grad()
+def text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0):
+    """TextRNN.infer_sequence with the modules in train mode (what UNAST.cm_speech_in runs under no_grad): enc_outputs = ((h, c) [2,B,256],
+    enc_output [B,Tk,512]) or an encoder tape of either side, lens_k the live keys per sequence.  Returns Generated((tokens [B,T] int64, PAD past each
+    sequence's length, lens [B] int64)): T = max(lens) positions ran, a sequence that never drew EOS has length max_len.  The prenet's three
+    BatchNorms take T momentum updates (num_batches_tracked += T); the model's cached eval operands are dropped."""
+    from .network import TextRNN
+    from .utils import SOS_IDX, EOS_IDX
+    what = "text_generate_train"
+    tape, B, max_len = _begin_generation(what, model, TextRNN, TextDecoderPack, enc_outputs, lens_k, max_len, seed)
+    P, dev = tape.P, tape.enc.device
+    E = P.emb.shape[1]
+    if E % 64 or E > 256:
+        raise NotImplementedError("%s: an embedding width that is a multiple of 64, at most 256 (got %d)" % (what, E))
+    bns = [bn for _, _, _, bn in P.convs]
+    for bn in bns:
+        _check_bn(bn, what)
+    p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
+    st = _GenState(tape, max_len, S_GDROP)
+    rows = B * max_len
+    tape.site("g_emb_dropout", p_pre, S_GEMB, prefix_row0(B, max_len + 1), E)
+    for k in range(3):
+        tape.site("g_dropout%d" % (k + 1), p_pre, S_GPRE + k, prefix_row0(B, max_len + 1), 256)
+    tape.site("g_dropout_out", st.p_dec, S_GOUT, rows, 256)
+    tape.site("g_post_dropout", p_post, S_GPOST, rows, 256)
+    tokens = torch.zeros(B, max_len, dtype=torch.int64, device=dev)
+    zs = [_buf(rows, 256, dev=dev) for _ in range(3)]
+    parts = torch.empty(3 * ops.prefix_gen_tiles(B, max_len) * 512, dtype=torch.float64, device=dev)
+    pre, o2, logits = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev), _buf(B, P.ldh, dev=dev)
+    Ws = [(wp[0], bias) for wp, bias, _, _ in P.convs]
+
+    def one(i):
+        L = i + 1
+        row0 = prefix_row0(B, L)
+        part = parts[:3 * ops.prefix_gen_tiles(B, L) * 512].view(3, -1, 2, 256)
+        ops.prefix_gen_conv(Ws[0][0], Ws[0][1], zs[0], part[0], B, L, tokens=tokens, emb=P.emb, sos=SOS_IDX, drop_p=p_pre, seed=seed, stream_id=S_GEMB, row0=row0)
+        for k in (1, 2):
+            bn = bns[k - 1]
+            ops.prefix_gen_conv(Ws[k][0], Ws[k][1], zs[k], part[k], B, L, x=zs[k - 1], part_in=part[k - 1], bn=(bn.weight, bn.bias, bn.eps), drop_p=p_pre,
+                                seed=seed, stream_id=S_GPRE + k - 1, row0=row0)
+        ops.prefix_gen_finish(zs[2], part, bns, pre, B, L, running=st.running, drop_p=p_pre, seed=seed, stream_id=S_GPRE + 2, row0=row0)
+        tz = st.step(i, pre)
+        ops.prefix_gen_act_drop(tz, o2, ops.PGEN_TANH, drop_a=st.p_dec, stream_a=S_GOUT, drop_b=p_post, stream_b=S_GPOST, seed=seed, row0=i * B)
+        ops.rnn_linear(o2, P.head[0][0], P.head[1], logits)
+        ops.prefix_gen_end_text(logits, P.V, tokens, i, st.stop_lens, max_len, EOS_IDX, st.running)
+
+    steps = _run_positions(st, max_len, one)
+    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    host = torch.cat([st.stop_lens.view(B, 1), tokens[:, :steps]], 1).cpu()                 # the one read-back after the loop: lengths and tokens
+    lens_host = [int(v) for v in host[:, 0]]
+    T = max(lens_host)
+    live = torch.arange(T)[None, :] < host[:, :1]
+    out = Generated((tokens[:, :T] * live.to(dev), st.stop_lens))
+    out.lens_host, out.steps, out.sites, out.max_len = lens_host, steps, tape.sites, max_len
+    out.live_pad = int(((host[:, 1:T + 1] == PAD_IDX) & live).sum())
+    return out
+
+
+@torch.no_grad()
+def speech_generate_train(model, enc_outputs, lens_k, max_len=815, seed=0):
+    """SpeechRNN.infer_sequence with the modules in train mode (what UNAST.cm_text_in runs under no_grad).  Returns Generated((pre, post [B,T,M],
+    stop [B,T], lens [B] int64)), zero past each sequence's length: T = max(lens), a sequence whose stop logit never reached sigmoid >= .5 has
+    length max_len.  The post-net runs once over all B (T+1) frames, go frame and stopped sequences' frames included, and is masked afterwards
+    (its BatchNorms take one update); the model's cached eval operands are dropped."""
+    from .network import SpeechRNN
+    what = "speech_generate_train"
+    tape, B, max_len = _begin_generation(what, model, SpeechRNN, DecoderPack, enc_outputs, lens_k, max_len, seed)
+    P, dev, M = tape.P, tape.enc.device, tape.P.M
+    p_pre = float(model.prenet.p)
+    st = _GenState(tape, max_len, S_SGDROP)
+    rows = B * max_len
+    (w1, b1, _), (w2, b2, _) = P.fcs
+    tape.site("g_prenet_dropout", p_pre, S_SGPRE, rows, w1[0].shape[0])
+    tape.site("g_dropout_out", st.p_dec, S_SGOUT, rows, 256)
+    frames = torch.zeros(B, max_len + 1, M, dtype=_F32, device=dev)                         # position 0 = the all-zero go frame
+    stops = torch.zeros(B, max_len, dtype=_F32, device=dev)
+    a1, h1, pre = _buf(B, w1[0].shape[0], dev=dev), _buf(B, w1[0].shape[0], dev=dev), _buf(B, 256, dev=dev)
+    head = _buf(B, P.ldh, dev=dev)
+
+    def one(i):
+        ops.rnn_linear(frames[:, i], w1[0], b1, a1)
+        ops.prefix_gen_act_drop(a1, h1, ops.PGEN_RELU, drop_a=p_pre, stream_a=S_SGPRE, seed=seed, row0=i * B)
+        ops.rnn_linear(h1, w2[0], b2, pre, act=1)
+        tz = st.step(i, pre)
+        ops.prefix_gen_act_drop(tz, st.o, ops.PGEN_TANH, drop_a=st.p_dec, stream_a=S_SGOUT, seed=seed, row0=i * B)
+        ops.rnn_linear(st.o, P.head[0][0], P.head[1], head)
+        ops.prefix_gen_end_speech(head, M, frames, stops, i, st.stop_lens, max_len, st.running)
+
+    steps = _run_positions(st, max_len, one)
+    lens_host = [int(v) for v in st.stop_lens.tolist()]                                     # the one read-back after the loop
+    T = max(lens_host)
+    outs = frames[:, :T + 1].contiguous()
+    post = _postnet_forward(tape, outs, S_SGPOST, what)
+    live = (torch.arange(T, device=dev)[None, :] < st.stop_lens[:, None]).to(_F32)
+    out = Generated((outs[:, 1:] * live[:, :, None], post[:, 1:] * live[:, :, None], stops[:, :T] * live, st.stop_lens))
+    out.lens_host, out.steps, out.sites, out.max_len = lens_host, steps, tape.sites, max_len
+    return out

@@ -18,10 +18,12 @@ scheme; train_rnn._prepare_grads keeps such a .grad in place).  A segment whose 
 skipped entirely -- no decay, no moment update, no step count, no share in the clip norm: torch.optim's `grad is None`.  'Produced' is
 tracked on the host (model._rnn_touched, FlatStore.touched).
 
-Out of scope (raise NotImplementedError): the cross-model step (UNAST.cm_text_in / cm_speech_in generate in TRAIN mode: dropout inside greedy
-decoding and TextPrenet normalising every generated prefix with its own batch statistics, which the eval generation here does not do),
-evaluate(), graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step called directly (they would have to return
-autograd-connected losses).
+The cross-model (back-translation) step is train_cm_step below, and train_step here is the step with cm_steps >= 0: both are explicit
+entry points of this module.  unast_amd.train's own train_cm_step / crossmodel_step / train(args) with cm_steps > 0 keep raising CM_REASON for
+model_type='rnn' (flipping that dispatch is a follow-up).
+
+Out of scope (raise NotImplementedError): evaluate(), graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step /
+crossmodel_step called directly (they would have to return autograd-connected losses).
 """
 import math
 
@@ -32,9 +34,11 @@ from .utils import is_deterministic, next_seed, specaugment
 
 _F32 = torch.float32
 GEN_SEGMENTS = ("text_m", "speech_m")
-CM_REASON = ("the cross-model step is not built for model_type='rnn': UNAST.cm_text_in / cm_speech_in generate in train mode -- dropout is on "
-             "inside greedy decoding and TextPrenet normalises each generated prefix [SOS, c0, ..] with its own batch statistics at every "
-             "position -- which the eval generation of this path does not do; train with cm_steps = 0")
+CM_REASON = ("the cross-model step is not built for model_type='rnn' behind this entry point: UNAST.cm_text_in / cm_speech_in generate in train mode "
+             "-- dropout is on inside greedy decoding and TextPrenet normalises each generated prefix [SOS, c0, ..] with its own batch statistics at "
+             "every position -- which the eval generation of this path does not do; train with cm_steps = 0, or call the explicit entry points "
+             "unast_amd.train_rnn_step.train_cm_step / unast_amd.train_rnn_step.train_step, which generate with "
+             "unast_amd.train_rnn.text_generate_train / speech_generate_train")
 DIRECT_REASON = ("%s is not built for model_type='rnn' (the RNN generators are explicit tape calls under torch.no_grad(); it would have to return "
                  "autograd-connected losses): call %s, which runs the forward, the losses and the backward into .grad")
 RECORD = False          # True (tests): every sub-step leaves its tapes, permutation and discriminator batch in model._rnn_step_record
@@ -353,10 +357,11 @@ def _speech_loss(tape, gold, lens_i32, eos_weight, gs):
     return loss, dh[:, :, :P.M], dp, dh[:, :, P.M]
 
 
-def _generator_substep(losses, keys, model, args, accum_steps, text, mel, ml_dev, tl_dev, te, se, td, sd, td_mem, sd_mem):
-    """What the two generator sub-steps share once their four tapes exist: the losses, the discriminator term on the two encoder outputs, and
+def _generator_substep(losses, keys, model, args, accum_steps, text, mel, ml_dev, tl_dev, te, se, td, sd, td_mem, sd_mem, enc_lens=None):
+    """What the generator sub-steps share once their four tapes exist: the losses, the discriminator term on the two encoder outputs, and
     the backward.  te / se: the text / speech encoder tapes; td / sd: the text / speech decoder tapes; td_mem / sd_mem: the encoder tape each
-    decoder attended to, which receives its cotangents."""
+    decoder attended to, which receives its cotangents.  enc_lens (the cross-model step): the (text, speech) lengths of what the two encoders
+    read -- the generated sequences' -- where they differ from the targets' tl_dev / ml_dev."""
     from . import train as T
     dev = text.device
     gs = _gscale(dev, accum_steps)
@@ -369,7 +374,8 @@ def _generator_substep(losses, keys, model, args, accum_steps, text, mel, ml_dev
     parts = [t_loss, s_loss]
     dth = dsh = None
     if args.use_discriminator:
-        d_loss, dth, dsh = _discriminator_term(model, te, tl_dev, se, ml_dev, gs, False, rec)
+        d_tl, d_sl = enc_lens if enc_lens is not None else (tl_dev, ml_dev)
+        d_loss, dth, dsh = _discriminator_term(model, te, d_tl, se, d_sl, gs, False, rec)
         parts.append(d_loss.view(1))
     cots = {id(td_mem): train_rnn.text_decoder_backward(td, d_logits, accumulate=True),
             id(sd_mem): train_rnn.decoder_backward(sd, d_pre, d_post, d_stop, accumulate=True)}
@@ -440,3 +446,65 @@ def train_discriminator_step(losses, model, batch, step, accum_steps, args, log_
         ops.scalar_combine([d_loss.view(())], float(accum_steps), out)
     losses['d'].append(T._log(d_loss.view(())))
     return out
+
+
+# ---- the cross-model (back-translation) sub-step and the step that includes it; DESIGN 5m ----------------------------------------------------------
+TEXT_MAX_LEN, SPEECH_MAX_LEN = 300, 815                    # infer_sequence's defaults (src/network.py:312, 586): what cm_speech_in / cm_text_in generate with
+
+
+def train_cm_step(losses, model, batch, step, accum_steps, args):
+    """src/train.py:418-444 with crossmodel_step (261-294) and UNAST.cm_speech_in / cm_text_in (src/network.py:103-123), speech-in first:
+      speech-in: speech encoder (train mode, no noise) -> greedy text generation in train mode, both without backward; then the text encoder on
+                 the generated tokens -> the teacher-forced speech decoder -> speech_loss ('s_cm');
+      text-in:   text encoder -> greedy speech generation in train mode, without backward; then the speech encoder on the generated post-net
+                 frames -> the teacher-forced text decoder -> text_loss ('t_cm');
+    and the discriminator term ('d_cm', frozen discriminator, flipped targets) on the two re-encoded outputs with the generated lengths.
+    Gradients stop at the generated sequences.  A generated PAD id inside a sequence's length stays an attention key here (the kernels mask by
+    length; the reference masks text.eq(PAD)): model._rnn_cm_live_pad counts them for the last call."""
+    _check(model, args)
+    text, mel, tl, ml, tl_dev, ml_dev = _process(batch)
+    tm, sm = model.text_m, model.speech_m
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=text.device)                      # noqa: E731
+    with torch.no_grad():
+        seeds = [next_seed() for _ in range(8)]
+        s_mem = train_rnn.encoder_forward(sm, mel, ml, seed=seeds[0])
+        gen_t = train_rnn.text_generate_train(tm, s_mem, ml, max_len=TEXT_MAX_LEN, seed=seeds[1])
+        te = train_rnn.encoder_forward(tm, gen_t[0], gen_t.lens_host, seed=seeds[2])
+        sd = train_rnn.decoder_forward(sm, mel, te, gen_t.lens_host, seed=seeds[3])
+        t_mem = train_rnn.encoder_forward(tm, text, tl, seed=seeds[4])
+        gen_s = train_rnn.speech_generate_train(sm, t_mem, tl, max_len=SPEECH_MAX_LEN, seed=seeds[5])
+        se = train_rnn.encoder_forward(sm, gen_s[1], gen_s.lens_host, seed=seeds[6])
+        td = train_rnn.text_decoder_forward(tm, text, se, gen_s.lens_host, seed=seeds[7])
+        model.__dict__["_rnn_cm_live_pad"] = gen_t.live_pad
+        out = _generator_substep(losses, ('t_cm', 's_cm', 'd_cm'), model, args, accum_steps, text, mel, ml_dev, tl_dev, te, se, td, sd, se, te,
+                                 enc_lens=(i32(gen_t.lens_host), i32(gen_s.lens_host)))
+        if RECORD:
+            model._rnn_step_record.update(gen_text=gen_t, gen_speech=gen_s, seeds=seeds, live_pad=gen_t.live_pad, mem_tapes=dict(speech_mem=s_mem, text_mem=t_mem))
+        return out
+
+
+def train_step(losses, model, optimizer, scheduler, batches, step, args):
+    """One iteration of train()'s hot loop (src/train.py:602-655) for model_type == 'rnn' with cm_steps >= 0, as unast_amd.train.train_step runs it
+    with cm_steps = 0: the discriminator frozen, ae_steps AE sub-steps on batches['unsup'], cm_steps cross-model sub-steps on batches['cm'],
+    sp_steps supervised sub-steps on batches['sup'] (every gradient scaled by 1 / their number), optimizer_step; then the discriminator
+    unfrozen, d_steps discriminator sub-steps on batches['disc'] and its optimizer_step.  Eager, on the current stream."""
+    # (the body of unast_amd.train.train_step's RNN branch plus the cm sub-steps: the two merge when train's dispatch stops refusing cm_steps > 0)
+    from . import train as T
+    _check(model, args)
+    cm_steps = getattr(args, "cm_steps", 0)
+    if args.use_discriminator:
+        T.freeze_model_parameters(model.discriminator)
+    accum_steps = args.ae_steps + cm_steps + args.sp_steps
+    subs = [(train_ae_step, batches["unsup"][si]) for si in range(args.ae_steps)]
+    subs += [(train_cm_step, batches["cm"][si]) for si in range(cm_steps)]
+    subs += [(train_sp_step, batches["sup"][si]) for si in range(args.sp_steps)]
+    for fn, b in subs:
+        fn(losses, model, b, step, accum_steps, args)
+    optimizer_step(model, optimizer, args)
+    if args.use_discriminator:
+        T.unfreeze_model_parameters(model.discriminator)
+        for si in range(args.d_steps):
+            train_discriminator_step(losses, model, batches["disc"][si], step, args.d_steps, args)
+        optimizer_step(model, optimizer, args)
+    if scheduler is not None:
+        scheduler.step()

@@ -234,6 +234,35 @@ def test_accumulate_overwrite_and_single_use(side):
     assert all(g.abs().max().item() == 0.0 for g in _grads(model).values())
 
 
+# ---- 3b. the three operand caches ---------------------------------------------------------------------------------------------------------------
+def test_operand_caches_rebuild_on_their_own_tensors_only_and_drop_together():
+    """Each of the three packs is cached in its slot of the model's __dict__, keyed on the version counters of its own tensor list: the same
+    object until one of those tensors is written in place, untouched by a write outside the list; drop_cached_operands clears every slot."""
+    from types import SimpleNamespace
+    from unast_amd import rnn, train_rnn, train_rnn_step
+    assert rnn.PACK_SLOTS == ("_rnn_pack", "_rnn_train_pack", "_rnn_decoder_train_pack")
+    tm, sm = _model("text")[0], _model("speech")[0]
+    for m, side, dec_cls, outside in ((tm, "text", train_rnn.TextDecoderPack, tm.postnet.fc1.weight),
+                                      (sm, "speech", train_rnn.DecoderPack, sm.postnet.linear_project.weight)):
+        caches = (("_rnn_pack", lambda: rnn.pack_of(m, side), m.decoder.linear_projection.linear_layer.bias),
+                  ("_rnn_train_pack", lambda: train_rnn.train_pack_of(m, side), m.encoder.reduce_h_W.bias),
+                  ("_rnn_decoder_train_pack", lambda: train_rnn.decoder_pack_of(m, dec_cls), next(m.postnet.parameters())))
+        for slot, get, own in caches:
+            first = get()
+            assert get() is first and m.__dict__[slot][1] is first, slot
+            with torch.no_grad():
+                own.add_(0)
+            second = get()
+            assert second is not first and get() is second, slot
+        enc_pack = train_rnn.train_pack_of(m, side)
+        with torch.no_grad():
+            outside.add_(0)                                   # a postnet parameter: not in the encoder train pack's list
+        assert train_rnn.train_pack_of(m, side) is enc_pack
+        assert set(rnn.PACK_SLOTS) <= set(m.__dict__)
+    train_rnn_step.drop_cached_operands(SimpleNamespace(text_m=tm, speech_m=sm))
+    assert not set(rnn.PACK_SLOTS) & (set(tm.__dict__) | set(sm.__dict__))
+
+
 # ---- 4. the eval path is untouched -----------------------------------------------------------------------------------------------------------------
 def test_eval_encode_after_a_train_call():
     from unast_amd.network import TextRNN

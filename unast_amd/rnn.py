@@ -9,6 +9,8 @@ for a position, state in device memory (position, LSTM states, attention state),
 rule off.  What the kernels read is a derived, cached copy of the parameters (`Pack`), rebuilt when a parameter's or buffer's version counter
 moves: eval BatchNorm folded into tap-major conv weights, W_ih of both encoder directions as one matrix, W_hh in MFMA fragment order,
 [linear_project | stop_linear] as one head, and beside each GEMM / conv weight the residual the split-bf16 operand preparation drops.
+The train packs of unast_amd.train_rnn derive the same operands through the extractors in front of `Pack` and live in the same version-keyed
+cache (`cached_operands`, one slot of PACK_SLOTS per pack); each pack adds only what its own kernels read.
 Every contraction keeps fp32-level products (greedy trajectories are held to the reference's own fp32 error): unast_rnn_linear for the few rows of a
 step, the three-launch split form (_linear_rows, _conv) around the many-row GEMMs and convs.
 """
@@ -31,46 +33,92 @@ def _c(t):
     return t.detach().contiguous()
 
 
+# ---- what the eval pack and the train packs (unast_amd.train_rnn) derive alike: each function returns the common part, a pack adds its own --------
+LSTM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+def encoder_layers(enc):
+    """RNNEncoder's LSTM, layer by layer (a generator: a pack's own launches for a layer follow that layer's): the four parameters of each
+    direction, (W_ih of both directions as one matrix with its residual, W_hh in MFMA fragment order, b_ih, b_hh) as unast_lstm_seq_fwd reads
+    them, and the stacked W_hh (the train pack derives the backward's fragment order from it)."""
+    for l in range(enc.num_layers):
+        dirs = [tuple(getattr(enc.rnn, "%s_l%d%s" % (n, l, s)) for n in LSTM_NAMES) for s in ("", "_reverse")]
+        w_ih, w_hh, b_ih, b_hh = zip(*dirs)
+        whh = torch.stack(w_hh)
+        yield dirs, (_resid(torch.cat(w_ih)), ops.lstm_whh_fragments(whh), torch.cat(b_ih).detach().contiguous(), torch.cat(b_hh).detach().contiguous()), whh
+
+
+def encoder_reduce(enc):
+    """reduce_h_W, reduce_c_W as (weight, bias, module)."""
+    return [(_c(lin.weight), _c(lin.bias), lin) for lin in (enc.reduce_h_W, enc.reduce_c_W)]
+
+
+def attention_operands(dec):
+    """The attention layer, Luong (anything but 'lsa') or location-sensitive: its operands under the attribute names every pack gives them,
+    and the modules they come from (query, memory, v, location conv, location dense; the last two None for Luong)."""
+    at = dec.attention_layer
+    if dec.attention == "lsa":
+        mode, mods = ops.ATTN_LSA, (at.query_layer.linear_layer, at.memory_layer.linear_layer, at.v.linear_layer,
+                                    at.location_layer.location_conv.conv, at.location_layer.location_dense.linear_layer)
+    else:
+        mode, mods = ops.ATTN_LUONG, (at.project_hid, at.project_eo, at.fc2, None, None)
+    q, mem, v, conv, dense = mods
+    return dict(mode=mode, Wq=_c(q.weight), Wmem=_resid(mem.weight), v=_c(v.weight).view(-1), conv_w=_c(conv.weight) if conv is not None else None,
+                dense_w=_c(dense.weight) if dense is not None else None), mods
+
+
+def text_prenet_stages(pn):
+    """TextPrenet's three (conv, BatchNorm) stages: folded by the eval pack, kept apart (tap-major weight, batch statistics) by the train packs."""
+    return [(getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+
+
+def speech_postnet_stages(po):
+    """SpeechPostnet's four (conv, BatchNorm) stages in front of conv2."""
+    return [(po.conv1.conv, po.pre_batchnorm)] + [(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
+
+
+def tap_major(conv):
+    """A Conv1d's weight as the tap kernels read it ([Cout, taps, Cin]) with its residual, and its bias."""
+    return _resid(conv.weight.detach().permute(0, 2, 1)), _c(conv.bias)
+
+
+def speech_prenet_linears(prenet):
+    """SpeechPrenet's fc1, fc2 as (weight with its residual, bias, module)."""
+    return [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (prenet.layer.fc1, prenet.layer.fc2)]
+
+
+def padded_head(*linears):
+    """The given linears' rows as one head, zero rows added up to a multiple of 4 (the pitch the train paths' loss kernels read):
+    (((Wh, its residual), bh), ldh)."""
+    W, b = (torch.cat([getattr(lin, n).detach() for lin in linears]) for n in ("weight", "bias"))
+    pad = -W.shape[0] % 4
+    return (_resid(torch.nn.functional.pad(W, (0, 0, 0, pad))), torch.nn.functional.pad(b, (0, pad))), W.shape[0] + pad
+
+
 class Pack:
-    """The operands the kernels read, derived from one model's parameters (module docstring)."""
+    """The operands the eval kernels read, derived from one model's parameters (module docstring)."""
 
     def __init__(self, m, side):
         with torch.no_grad():
             enc, dec = m.encoder, m.decoder
-            self.enc = []
-            for l in range(enc.num_layers):
-                sfx = ("_l%d" % l, "_l%d_reverse" % l)
-                g = lambda n: [getattr(enc.rnn, n + s) for s in sfx]                       # noqa: E731
-                self.enc.append((_resid(torch.cat(g("weight_ih"))), ops.lstm_whh_fragments(torch.stack(g("weight_hh"))),
-                                 torch.cat(g("bias_ih")).contiguous(), torch.cat(g("bias_hh")).contiguous()))
-            self.reduce_h = (_c(enc.reduce_h_W.weight), _c(enc.reduce_h_W.bias))
-            self.reduce_c = (_c(enc.reduce_c_W.weight), _c(enc.reduce_c_W.bias))
-            self.dec = [tuple(_c(getattr(dec.rnn, n + "_l%d" % l)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(dec.num_layers)]
-            at = dec.attention_layer
-            if dec.attention == "lsa":
-                self.mode = ops.ATTN_LSA
-                self.Wq, self.Wmem, self.v = _c(at.query_layer.linear_layer.weight), _resid(at.memory_layer.linear_layer.weight), _c(at.v.linear_layer.weight).view(-1)
-                self.conv_w, self.dense_w = _c(at.location_layer.location_conv.conv.weight), _c(at.location_layer.location_dense.linear_layer.weight)
-            else:
-                self.mode = ops.ATTN_LUONG
-                self.Wq, self.Wmem, self.v = _c(at.project_hid.weight), _resid(at.project_eo.weight), _c(at.fc2.weight).view(-1)
-                self.conv_w = self.dense_w = None
+            self.enc = [operands for _, operands, _ in encoder_layers(enc)]
+            self.reduce_h, self.reduce_c = ((w, b) for w, b, _ in encoder_reduce(enc))
+            self.dec = [tuple(_c(getattr(dec.rnn, n + "_l%d" % l)) for n in LSTM_NAMES) for l in range(dec.num_layers)]
+            vars(self).update(attention_operands(dec)[0])              # mode, Wq, Wmem, v, conv_w, dense_w
             self.proj = (_c(dec.linear_projection.linear_layer.weight), _c(dec.linear_projection.linear_layer.bias))
             if side == "text":
-                pn = m.prenet
-                self.emb = _c(pn.embed.weight)
-                self.convs = [_fold_resid(getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+                self.emb = _c(m.prenet.embed.weight)
+                self.convs = [_fold_resid(conv, bn) for conv, bn in text_prenet_stages(m.prenet)]
                 self.head = (_c(m.postnet.fc1.weight), _c(m.postnet.fc1.bias))
                 self.head_rows = _resid(m.postnet.fc1.weight)
             else:
-                pn, po = m.prenet.layer, m.postnet
-                self.fc1 = (_c(pn.fc1.linear_layer.weight), _c(pn.fc1.linear_layer.bias))
-                self.fc2 = (_c(pn.fc2.linear_layer.weight), _c(pn.fc2.linear_layer.bias))
-                self.fc1_rows, self.fc2_rows = _resid(pn.fc1.linear_layer.weight), _resid(pn.fc2.linear_layer.weight)
+                po = m.postnet
+                (self.fc1_rows, b1, _), (self.fc2_rows, b2, _) = speech_prenet_linears(m.prenet)
+                self.fc1, self.fc2 = (self.fc1_rows[0], b1), (self.fc2_rows[0], b2)
                 self.head = (torch.cat([po.linear_project.weight, po.stop_linear.weight]).contiguous(),
                              torch.cat([po.linear_project.bias, po.stop_linear.bias]).contiguous())
-                self.post = [_fold_resid(po.conv1.conv, po.pre_batchnorm)] + [_fold_resid(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
-                self.post_out = (_resid(po.conv2.conv.weight.detach().permute(0, 2, 1)), _c(po.conv2.conv.bias))
+                self.post = [_fold_resid(conv, bn) for conv, bn in speech_postnet_stages(po)]
+                self.post_out = tap_major(po.conv2.conv)
 
 
 def _fold_resid(conv, bn):
@@ -78,17 +126,28 @@ def _fold_resid(conv, bn):
     return _resid(w), b
 
 
-def pack_of(m, side):
-    ver, dev = 0, None
-    for t in list(m.parameters()) + list(m.buffers()):
-        ver += t._version
-        dev = t.device
-    key = (ver, dev)
-    cached = m.__dict__.get("_rnn_pack")
+# ---- the version-keyed caches of derived operands: one slot in a model's __dict__ per pack ---------------------------------------------------
+EVAL_SLOT, ENCODER_TRAIN_SLOT, DECODER_TRAIN_SLOT = PACK_SLOTS = ("_rnn_pack", "_rnn_train_pack", "_rnn_decoder_train_pack")
+
+
+def cached_operands(m, slot, tensors, build):
+    """m's pack in `slot`, built by build() and rebuilt when the version counter of one of `tensors` has moved (or the device changed)."""
+    key = (sum(t._version for t in tensors), tensors[-1].device if tensors else None)
+    cached = m.__dict__.get(slot)
     if cached is None or cached[0] != key:
-        cached = (key, Pack(m, side))
-        m.__dict__["_rnn_pack"] = cached
+        cached = (key, build())
+        m.__dict__[slot] = cached
     return cached[1]
+
+
+def pack_of(m, side):
+    return cached_operands(m, EVAL_SLOT, list(m.parameters()) + list(m.buffers()), lambda: Pack(m, side))
+
+
+def drop_eval_pack(m):
+    """For the train-mode forwards: their kernels write the BatchNorm running statistics behind torch's version counters, so the cached eval
+    operands (which fold those statistics) are dropped rather than left to the key."""
+    m.__dict__.pop(EVAL_SLOT, None)
 
 
 def _resid(w):

@@ -21,13 +21,14 @@ SpeechRNN's decoder trains through two more entry points with the same conventio
 so that the speech autoencoder is encoder_forward -> decoder_forward -> decoder_backward -> encoder_backward(..., accumulate=True).
 
 TextRNN's decoder trains through the last pair (the end of this file); both decoders run the same position loop
-(_loop_forward / _loop_backward), each supplying its own prenet rows and head:
+(_loop_forward / _loop_backward), each supplying its own prenet rows and head.  The packs (TrainPack for the encoders, DecoderPack /
+TextDecoderPack over _LoopPack for the decoders) are built from unast_amd.rnn's extractors and cached by its cached_operands:
 
     tape = text_decoder_forward(model, target, enc_outputs, lens_k, seed=0) # tape.logits [B,T,len(symbols)], tape.sites
     d_enc_output, d_h, d_c = text_decoder_backward(tape, d_logits)          # writes p.grad of model.prenet, model.decoder, model.postnet
 
 Greedy generation in TRAIN mode -- infer_sequence as UNAST.cm_speech_in / cm_text_in run it under no_grad with the modules in train() -- is the
-last section; no backward, no tape:
+last section; no backward, no tape, and the same position as the teacher-forced loop's (_TrainCell):
 
     tokens, lens = text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0)
     pre, post, stop, lens = speech_generate_train(model, enc_outputs, lens_k, max_len=815, seed=0)
@@ -36,9 +37,9 @@ import collections
 
 import torch
 
-from . import ops
+from . import ops, rnn
 from .rnn import _buf, _c, _conv, _linear_rows, _resid
-from .utils import PAD_IDX
+from .utils import EOS_IDX, PAD_IDX, SOS_IDX
 
 _F32 = torch.float32
 NOISE_P = 0.3                     # noise_fn's mask_p (src/utils.py:40)
@@ -53,37 +54,18 @@ class TrainPack:
     use rnn.Pack's folded conv weights)."""
 
     def __init__(self, m, side):
-        enc = m.encoder
-        self.layers = []
-        for l in range(enc.num_layers):
-            sfx = ("_l%d" % l, "_l%d_reverse" % l)
-            g = lambda n: [getattr(enc.rnn, n + s) for s in sfx]                        # noqa: E731
-            whh = torch.stack(g("weight_hh"))
-            self.layers.append(dict(w_ih=_resid(torch.cat(g("weight_ih"))), wfrag=ops.lstm_whh_fragments(whh), wfrag_t=ops.lstm_whh_fragments_bwd(whh),
-                                    b_ih=torch.cat(g("bias_ih")).detach().contiguous(), b_hh=torch.cat(g("bias_hh")).detach().contiguous(),
-                                    params=[tuple(getattr(enc.rnn, n + s) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for s in sfx]))
-        self.reduce = [(_c(lin.weight), _c(lin.bias), lin.weight.detach().t().contiguous(), lin) for lin in (enc.reduce_h_W, enc.reduce_c_W)]
+        self.layers = [dict(w_ih=w_ih, wfrag=wfrag, wfrag_t=ops.lstm_whh_fragments_bwd(whh), b_ih=b_ih, b_hh=b_hh, params=dirs)
+                       for dirs, (w_ih, wfrag, b_ih, b_hh), whh in rnn.encoder_layers(m.encoder)]
+        self.reduce = [(w, b, lin.weight.detach().t().contiguous(), lin) for w, b, lin in rnn.encoder_reduce(m.encoder)]
         if side == "text":
-            pn = m.prenet
-            self.emb = _c(pn.embed.weight)
-            self.convs = [(_resid(getattr(pn, "conv%d" % i).conv.weight.detach().permute(0, 2, 1)), _c(getattr(pn, "conv%d" % i).conv.bias),
-                           getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+            self.emb = _c(m.prenet.embed.weight)
+            self.convs = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(m.prenet)]   # (tap-major weight pair, bias, conv, bn)
         else:
-            pn = m.prenet.layer
-            self.fcs = [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (pn.fc1, pn.fc2)]
+            self.fcs = rnn.speech_prenet_linears(m.prenet)
 
 
 def train_pack_of(m, side):
-    ver, dev = 0, None
-    for t in list(m.prenet.parameters()) + list(m.encoder.parameters()):
-        ver += t._version
-        dev = t.device
-    key = (ver, dev)
-    cached = m.__dict__.get("_rnn_train_pack")
-    if cached is None or cached[0] != key:
-        cached = (key, TrainPack(m, side))
-        m.__dict__["_rnn_train_pack"] = cached
-    return cached[1]
+    return rnn.cached_operands(m, rnn.ENCODER_TRAIN_SLOT, _encoder_params(m), lambda: TrainPack(m, side))
 
 
 class Tape:
@@ -182,24 +164,7 @@ def encoder_forward(model, x, lens, noise_in=False, seed=0):
         tape.site("noise", noise_p, S_NOISE, N, 1, "row")
         tape.ids = ids
         tape.pad_mask = ids.eq(PAD_IDX)
-        C = 256
-        tape.xs, tape.zs = [x0], []
-        tape.mean, tape.rstd = _buf(3, C, dev=dev), _buf(3, C, dev=dev)
-        bn_ws = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        cur = x0.view(B, T, -1)
-        for i, (wp, bias, _, bn) in enumerate(P.convs):
-            if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-                raise NotImplementedError("encoder_forward: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)")
-            z = _conv(cur, wp, bias, 2)
-            y = _buf(N, C, dev=dev)
-            ops.bn_fwd(z.view(N, C), bn.weight, bn.bias, y, tape.mean[i], tape.rstd[i], bn.running_mean, bn.running_var, bn_ws, 1, drop_p=p, seed=seed,
-                       stream_id=S_PRE1 + i, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
-            tape.site("dropout%d" % (i + 1), p, S_PRE1 + i, N, C)
-            tape.zs.append(z.view(N, C))
-            tape.xs.append(y)
-            cur = y.view(B, T, C)
-        model.__dict__.pop("_rnn_pack", None)              # the running statistics moved under the cached eval operands (kernel writes)
-        front = tape.xs[3]
+        front = _bn_stages_forward(tape, x0.view(B, T, -1), P.convs, 2, 1, p, S_PRE1, ["dropout1", "dropout2", "dropout3"], "encoder_forward")
     else:
         mel = model._mel(x)
         B, T, M = mel.shape
@@ -318,25 +283,11 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
         p = float(model.prenet.p)
         bn_ws = torch.empty(2 * C, dtype=torch.float64, device=dev)
         for i in (2, 1, 0):
-            (wp, wr), _, conv, bn = P.convs[i]
+            wpair, _, conv, bn = P.convs[i]
             dz = _buf(N, C, dev=dev)
             ops.bn_bwd(dy, tape.zs[i], tape.mean[i], tape.rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 1, drop_p=p, seed=seed,
                        stream_id=S_PRE1 + i)
-            xin = tape.xs[i]
-            Cin = xin.shape[1]
-            dz, dzh, dzr = (t.view(B, T, C) for t in _parts(dz))
-            gw = torch.zeros_like(wp)
-            x3, x3res = xin.view(B, T, Cin), _resid_of(xin).view(B, T, Cin)
-            ops.conv_taps_wgrad(dzh, x3, gw, 2)
-            ops.conv_taps_wgrad(dzr, x3, gw, 2)
-            ops.conv_taps_wgrad(dz, x3res, gw, 2)
-            conv.weight.grad.add_(gw.permute(0, 2, 1))
-            ops.colsum(dz.view(N, C), conv.bias.grad)
-            dx = _buf(B, T, Cin, dev=dev)
-            ops.conv_taps_dgrad(dzh, wp, dx, 2)
-            ops.conv_taps_dgrad(dzr, wp, dx, 2, beta=1)
-            ops.conv_taps_dgrad(dz, wr, dx, 2, beta=1)
-            dy = dx.view(N, Cin)
+            dy = _conv_grads(dz, tape.xs[i], B, T, wpair, conv, 2)
         noise_p = NOISE_P if tape.noise_in else 0.0
         ops.embed_bwd(tape.ids, dy, model.prenet.embed.weight.grad, T, drop_p=p, seed=seed, stream_id=S_EMB, noise_p=noise_p, noise_stream=S_NOISE,
                       padding_idx=model.prenet.embed.padding_idx)
@@ -382,17 +333,8 @@ class _LoopPack:
         self.bias = [_c(getattr(r, n)) for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1")]
         tr = lambda w: w.detach().t().contiguous()                                          # noqa: E731
         self.wt_ihc0, self.wt_hh0, self.wt_ih1, self.wt_hh1 = tr(w0[:, 256:]), tr(r.weight_hh_l0), tr(r.weight_ih_l1), tr(r.weight_hh_l1)
-        at = dec.attention_layer
-        if dec.attention == "lsa":
-            self.mode = ops.ATTN_LSA
-            self.q_lin, self.mem_lin, self.v_lin = at.query_layer.linear_layer, at.memory_layer.linear_layer, at.v.linear_layer
-            self.conv_mod, self.dense_lin = at.location_layer.location_conv.conv, at.location_layer.location_dense.linear_layer
-            self.conv_w, self.dense_w = _c(self.conv_mod.weight), _c(self.dense_lin.weight)
-        else:
-            self.mode = ops.ATTN_LUONG
-            self.q_lin, self.mem_lin, self.v_lin = at.project_hid, at.project_eo, at.fc2
-            self.conv_mod = self.dense_lin = self.conv_w = self.dense_w = None
-        self.Wq, self.Wmem, self.v = _c(self.q_lin.weight), _resid(self.mem_lin.weight), _c(self.v_lin.weight).view(-1)
+        operands, (self.q_lin, self.mem_lin, self.v_lin, self.conv_mod, self.dense_lin) = rnn.attention_operands(dec)
+        vars(self).update(operands)                                                         # mode, Wq, Wmem, v, conv_w, dense_w
         self.A = self.Wq.shape[0]
         if self.A % 4 or self.A > 64:
             raise NotImplementedError("%s: attn_dim must be a multiple of 4, at most 64 (got %d)" % (what, self.A))
@@ -405,21 +347,12 @@ class DecoderPack(_LoopPack):
 
     def __init__(self, m):
         super().__init__(m, "decoder_forward")
-        po, pn = m.postnet, m.prenet.layer
-        w0 = self.w_hh0
-        self.fcs = [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (pn.fc1, pn.fc2)]
-        M = po.linear_project.weight.shape[0]
-        self.M, self.ldh = M, (M + 1 + 3) // 4 * 4                                          # [linear_project | stop_linear | zero rows] as one head
-        Wh = torch.zeros(self.ldh, 256, dtype=_F32, device=w0.device)
-        bh = torch.zeros(self.ldh, dtype=_F32, device=w0.device)
-        Wh[:M].copy_(po.linear_project.weight.detach())
-        Wh[M].copy_(po.stop_linear.weight.detach()[0])
-        bh[:M].copy_(po.linear_project.bias.detach())
-        bh[M:M + 1].copy_(po.stop_linear.bias.detach())
-        self.head = (_resid(Wh), bh)
-        stages = [(po.conv1.conv, po.pre_batchnorm)] + [(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
-        self.post = [(_resid(conv.weight.detach().permute(0, 2, 1)), _c(conv.bias), conv, bn) for conv, bn in stages]
-        self.post_out = (_resid(po.conv2.conv.weight.detach().permute(0, 2, 1)), _c(po.conv2.conv.bias), po.conv2.conv)
+        po = m.postnet
+        self.fcs = rnn.speech_prenet_linears(m.prenet)
+        self.M = po.linear_project.weight.shape[0]
+        self.head, self.ldh = rnn.padded_head(po.linear_project, po.stop_linear)            # [linear_project | stop_linear | zero rows] as one head
+        self.post = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.speech_postnet_stages(po)]
+        self.post_out = rnn.tap_major(po.conv2.conv) + (po.conv2.conv,)
 
 
 def _decoder_params(model):
@@ -434,33 +367,18 @@ class TextDecoderPack(_LoopPack):
         super().__init__(m, "text_decoder_forward")
         pn, fc = m.prenet, m.postnet.fc1
         self.emb = _c(pn.embed.weight)
-        self.convs = [(_resid(getattr(pn, "conv%d" % i).conv.weight.detach().permute(0, 2, 1)), _c(getattr(pn, "conv%d" % i).conv.bias),
-                       getattr(pn, "conv%d" % i).conv, getattr(pn, "batch_norm%d" % i)) for i in (1, 2, 3)]
+        self.convs = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(pn)]
         E = self.emb.shape[1]
         if E % 4 or 256 % (E // 4) or any(tuple(wp[0].shape[::2]) != (256, cin) or wp[0].shape[1] != 5 for (wp, _, _, _), cin in zip(self.convs, (E, 256, 256))):
             raise NotImplementedError("text_decoder_forward: three 5-tap convs into 256 channels over an embedding whose width / 4 divides 256")
         if tuple(fc.weight.shape[1:]) != (256,):
             raise NotImplementedError("text_decoder_forward: TextPostnet.fc1 over 256 features")
         self.V = fc.weight.shape[0]
-        self.ldh = (self.V + 3) // 4 * 4
-        Wh = torch.zeros(self.ldh, 256, dtype=_F32, device=self.emb.device)
-        bh = torch.zeros(self.ldh, dtype=_F32, device=self.emb.device)
-        Wh[:self.V].copy_(fc.weight.detach())
-        bh[:self.V].copy_(fc.bias.detach())
-        self.head = (_resid(Wh), bh)
+        self.head, self.ldh = rnn.padded_head(fc)
 
 
 def decoder_pack_of(m, cls=DecoderPack):
-    ver, dev = 0, None
-    for t in _decoder_params(m):
-        ver += t._version
-        dev = t.device
-    key = (ver, dev)
-    cached = m.__dict__.get("_rnn_decoder_train_pack")
-    if cached is None or cached[0] != key:
-        cached = (key, cls(m))
-        m.__dict__["_rnn_decoder_train_pack"] = cached
-    return cached[1]
+    return rnn.cached_operands(m, rnn.DECODER_TRAIN_SLOT, _decoder_params(m), lambda: cls(m))
 
 
 class DecoderTape(Tape):
@@ -530,32 +448,37 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
 
 
 def _postnet_forward(tape, outs, stream0, what):
-    """SpeechPostnet in train mode over outs [B, T+1, M] (the go frame included, as the reference runs it): four conv + BatchNorm (batch
-    statistics over all B (T+1) rows, running statistics updated) + tanh + dropout stages and conv2, plus the residual.  Leaves the stages'
-    inputs and statistics on the tape (xs, zs, mean, rstd: what decoder_backward reads) and returns outs + postnet(outs) [B, T+1, M].
-    Shared by decoder_forward and speech_generate_train; stream0 = the first of the four dropout sites' stream ids."""
-    model, P, seed = tape.model, tape.P, tape.seed
-    B, T1, M = outs.shape
-    N1, dev = B * T1, outs.device
-    p_post = float(model.postnet.p)
-    tape.xs, tape.zs = [outs.view(N1, M)], []
-    tape.mean, tape.rstd = _buf(4, 256, dev=dev), _buf(4, 256, dev=dev)
+    """SpeechPostnet in train mode over outs [B, T+1, M] (the go frame included, as the reference runs it): four conv + BatchNorm + tanh +
+    dropout stages (_bn_stages_forward; stream0 = the first of their stream ids) and conv2, plus the residual.  Returns outs + postnet(outs)
+    [B, T+1, M].  Shared by decoder_forward and speech_generate_train."""
+    P, (B, T1, _) = tape.P, outs.shape
+    y = _bn_stages_forward(tape, outs, P.post, 4, 2, float(tape.model.postnet.p), stream0, ["post_dropout%d" % k for k in range(4)], what)
+    post = _conv(y.view(B, T1, 256), P.post_out[0], P.post_out[1], 4)
+    ops.add_inplace(post, outs)
+    return post
+
+
+def _bn_stages_forward(tape, cur, stages, pad_left, act, p, stream0, names, what):
+    """The conv + BatchNorm + activation (1 ReLU, 2 tanh) + dropout stages of TextPrenet / SpeechPostnet in train mode over cur [B,T,Cin]: batch
+    statistics over all B T rows, running statistics updated (so the cached eval operands are dropped).  Leaves the stages' inputs, conv outputs
+    and statistics on the tape (xs, zs, mean, rstd: what the backward reads) and the dropout sites `names`; returns the last output [B*T,256]."""
+    B, T, _ = cur.shape
+    N, dev = B * T, cur.device
+    tape.xs, tape.zs = [cur.view(N, -1)], []
+    tape.mean, tape.rstd = _buf(len(stages), 256, dev=dev), _buf(len(stages), 256, dev=dev)
     bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
-    cur = outs
-    for k, (wp, bias, _, bn) in enumerate(P.post):
+    for k, (wp, bias, _, bn) in enumerate(stages):
         _check_bn(bn, what)
-        z = _conv(cur, wp, bias, 4).view(N1, 256)
-        y = _buf(N1, 256, dev=dev)
-        ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, 2, drop_p=p_post, seed=seed,
+        z = _conv(cur, wp, bias, pad_left).view(N, 256)
+        y = _buf(N, 256, dev=dev)
+        ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, act, drop_p=p, seed=tape.seed,
                    stream_id=stream0 + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
-        tape.site("post_dropout%d" % k, p_post, stream0 + k, N1, 256)
+        tape.site(names[k], p, stream0 + k, N, 256)
         tape.zs.append(z)
         tape.xs.append(y)
-        cur = y.view(B, T1, 256)
-    post = _conv(cur, P.post_out[0], P.post_out[1], 4)
-    ops.add_inplace(post, outs)
-    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
-    return post
+        cur = y.view(B, T, 256)
+    rnn.drop_eval_pack(tape.model)
+    return y
 
 
 def _check_bn(bn, what):
@@ -591,44 +514,66 @@ def _begin_decoder_tape(what, model, pack_cls, enc_outputs, lens_k, B, T, seed, 
     return tape
 
 
+class _TrainCell:
+    """One decoder position in train mode (RNNDecoder.forward, src/module.py:362-374, up to the projection's input): attention, then the two
+    LSTM cells with the saved state the backward reads -- 7 launches.  The teacher-forced loop (_loop_forward: rows of [B,T,...] slabs) and the
+    train-mode generations (_GenState.step: ping-pong halves) each hand it views of where their rows live.
+    (The eval step rnn._Core.step stays apart: its kernels update the state in place and save nothing, and it splits the projection differently.)"""
+
+    def __init__(self, tape):
+        P, enc, B, Tk = tape.P, tape.enc, tape.B, tape.Tk
+        self.P, self.enc, self.lens, self.h0, self.c0 = P, enc, tape.lens, tape.h0, tape.c0
+        self.mem = _linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, P.A)       # memory-side projection, once for all positions
+        self.ga, self.gb = _buf(B, 1024, dev=enc.device), _buf(B, 1024, dev=enc.device)
+
+    def __call__(self, first, xp0, mask, h0d, q, w_in, w_out, cum_in, cum_out, ctx, h0_in, h0_out, s0, c0_in, s1, c1_in, h1_out):
+        """xp0 = W_ih_l0[:, :256] prenet + b_ih; mask / h0d: nn.LSTM's inter-layer dropout factors and the dropped h0_out (None with dropout off);
+        q: the top layer's h from BEFORE this position's LSTM (src/module.py:365); w_* / cum_* [B,Tk]: the attention weights and (lsa, else None)
+        their running sum, read / written; ctx, h0_out, h1_out: destinations; s0, s1 [B,5,256]: the layers' saved state, c0_in / c1_in their
+        previous cell states.  first: position 0 -- the encoder's final states stand in for q, c0_in and c1_in, which are not read."""
+        P, ga, gb = self.P, self.ga, self.gb
+        if first:
+            q, c0_in, c1_in = self.h0[1], self.c0[0], self.c0[1]
+        _, b_hh0, b_ih1, b_hh1 = P.bias
+        ops.rnn_attn_step_train(P.mode, q, P.Wq, self.mem, P.v, self.enc, self.lens, ctx, w_out, prev_in=w_in, cum_in=cum_in, cum_out=cum_out,
+                                conv_w=P.conv_w, dense_w=P.dense_w)
+        ops.rnn_linear(ctx, P.w_ih0_c, None, gb, R=xp0)                                     # LSTM input = [prenet | context] (src/module.py:367)
+        ops.rnn_linear(h0_in, P.w_hh0, b_hh0, ga, R=gb)
+        ops.lstm_cell_train(ga, c0_in, s0, h0_out, mask=mask, hd=h0d)
+        ops.rnn_linear(h0d if mask is not None else h0_out, P.w_ih1, b_ih1, gb)
+        ops.rnn_linear(q, P.w_hh1, b_hh1, ga, R=gb)
+        ops.lstm_cell_train(ga, c1_in, s1, h1_out)
+
+
 def _loop_forward(tape, pre, mark):
     """RNNDecoder over all positions, shared by both decoders: pre [B*T,256] = the prenet's row for every position (with teacher forcing it
     does not depend on the recurrence).  Hoists W_ih_l0[:, :256] pre + b_ih and the memory-side projection, runs the position loop, then
     the projection + tanh + dropout1 for all positions.  Keeps the loop's state on the tape; returns o [B*T,256], the head's input."""
-    model, P, B, T, Tk, seed, lens, enc, h0, c0 = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens, tape.enc, tape.h0, tape.c0
-    dev = enc.device
-    N, A, lsa = B * T, P.A, P.mode == ops.ATTN_LSA
+    model, P, B, T, Tk, seed = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed
+    dev = tape.enc.device
+    N, lsa = B * T, P.mode == ops.ATTN_LSA
     p_dec = float(model.decoder.p)
     xp0 = _linear_rows(pre, P.w_ih0_p, P.bias[0]).view(B, T, 1024)
-    mem = _linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, A)
-    tape.pre_act, tape.mem = pre, mem
+    cell = _TrainCell(tape)
+    tape.pre_act, tape.mem = pre, cell.mem
 
-    # ---- the loop: per position 7 launches on host-indexed slices of [B,T,...] slabs -------------------------------------------------------------
+    # ---- the loop: per position the cell's 7 launches on host-indexed slices of [B,T,...] slabs ------------------------------------------------
     Tkp = (Tk + 3) // 4 * 4
     W = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev)                                  # W[:, i+1] = w_i; W[:, 0] = 0 is position 0's prev
     CUM = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev) if lsa else None               # CUM[:, i] = what position i read
     HC = _buf(B, T, 768, dev=dev)                                                           # [h1_i | ctx_i]: the projection's input rows
     H0 = _buf(B, T + 1, 256, dev=dev)                                                       # H0[:, i] = layer 0's h before position i
-    H0[:, 0].copy_(h0[0])
+    H0[:, 0].copy_(tape.h0[0])
     S0, S1 = _buf(B, T, 5, 256, dev=dev), _buf(B, T, 5, 256, dev=dev)
     F1 = _drop_factor(p_dec, seed, S_DDROP, N, 256, dev).view(B, T, 256) if p_dec > 0.0 else None
     tape.site("d_drop0", p_dec, S_DDROP, N, 256)
     H0d = _buf(B, T, 256, dev=dev) if F1 is not None else None
-    ga, gb = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev)
-    b_ih0, b_hh0, b_ih1, b_hh1 = P.bias
     if mark is not None:
         mark("loop_begin")
-    for i in range(T):
-        q = HC[:, i - 1, :256] if i else h0[1]                                             # the top layer's h from BEFORE this position's LSTM
-        ops.rnn_attn_step_train(P.mode, q, P.Wq, mem, P.v, enc, lens, HC[:, i, 256:], W[:, i + 1, :Tk], prev_in=W[:, i, :Tk],
-                                cum_in=CUM[:, i, :Tk] if lsa else None, cum_out=CUM[:, i + 1, :Tk] if lsa else None, conv_w=P.conv_w, dense_w=P.dense_w)
-        ops.rnn_linear(HC[:, i, 256:], P.w_ih0_c, None, gb, R=xp0[:, i])
-        ops.rnn_linear(H0[:, i], P.w_hh0, b_hh0, ga, R=gb)
-        ops.lstm_cell_train(ga, S0[:, i - 1, 4] if i else c0[0], S0[:, i], H0[:, i + 1], mask=F1[:, i] if F1 is not None else None,
-                            hd=H0d[:, i] if F1 is not None else None)
-        ops.rnn_linear(H0d[:, i] if F1 is not None else H0[:, i + 1], P.w_ih1, b_ih1, gb)
-        ops.rnn_linear(q, P.w_hh1, b_hh1, ga, R=gb)
-        ops.lstm_cell_train(ga, S1[:, i - 1, 4] if i else c0[1], S1[:, i], HC[:, i, :256])
+    for i in range(T):                                                                      # (index -1 at i = 0: the cell does not read those views)
+        cell(i == 0, xp0[:, i], F1[:, i] if F1 is not None else None, H0d[:, i] if F1 is not None else None, HC[:, i - 1, :256], W[:, i, :Tk], W[:, i + 1, :Tk],
+             CUM[:, i, :Tk] if lsa else None, CUM[:, i + 1, :Tk] if lsa else None, HC[:, i, 256:], H0[:, i], H0[:, i + 1], S0[:, i], S0[:, i - 1, 4], S1[:, i],
+             S1[:, i - 1, 4], HC[:, i, :256])
     if mark is not None:
         mark("loop_end")
     tape.W, tape.CUM, tape.HC, tape.H0, tape.H0d, tape.S0, tape.S1, tape.F1 = W, CUM, HC, H0, H0d, S0, S1, F1
@@ -645,7 +590,7 @@ def _loop_forward(tape, pre, mark):
 
 
 def _conv_grads(dz2d, x2d, B, T, wpair, conv, pad_left):
-    """Weight, bias and input gradient of one tap-major conv with fp32-level products (the text prenet's form in encoder_backward)."""
+    """Weight, bias and input gradient of one tap-major conv with fp32-level products (the text prenets' and the post-net's backward)."""
     wp, wr = wpair
     C, Cin = dz2d.shape[1], x2d.shape[1]
     dz, dzh, dzr = (t.view(B, T, C) for t in _parts(dz2d))
@@ -874,7 +819,6 @@ def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     BatchNorm running statistics T times each (num_batches_tracked += T) and drops the model's cached eval operands.  mark (optional): called
     with 'prefix_begin' / 'prefix_end' around the prefix prenet and 'loop_begin' / 'loop_end' around the position loop."""
     from .network import TextRNN
-    from .utils import SOS_IDX
     if not isinstance(model, TextRNN):
         raise TypeError("text_decoder_forward: model must be a unast_amd.network.TextRNN (decoder_forward trains a SpeechRNN)")
     if not model.training:
@@ -924,7 +868,7 @@ def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
         if y is not None:
             tape.xs.append(y)
             cur = y
-    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    rnn.drop_eval_pack(model)
     if mark is not None:
         mark("prefix_end")
 
@@ -948,7 +892,6 @@ def text_decoder_backward(tape, d_logits, accumulate=False, mark=None):
     parameters under model.prenet, model.decoder and model.postnet (overwritten, or added to with accumulate=True; an existing dense fp32
     .grad is kept in place).  Returns (d_enc_output [B,Tk,512], d_h, d_c [2,B,256]), the cotangents encoder_backward takes.  A tape is used once.
     mark: as text_decoder_forward's."""
-    from .utils import SOS_IDX
     if not isinstance(tape, DecoderTape) or getattr(tape, "entry", None) != "text_decoder_forward":
         raise TypeError("text_decoder_backward: tape must come from text_decoder_forward")
     if tape.used:
@@ -1030,12 +973,16 @@ class _GenState:
         self.tape, self.lsa = tape, P.mode == ops.ATTN_LSA
         Tkp = (Tk + 3) // 4 * 4
         z = lambda *s: torch.zeros(*s, dtype=_F32, device=dev)                              # noqa: E731
-        self.mem = _linear_rows(tape.enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, P.A)
+        self.cell = _TrainCell(tape)
         self.W, self.CUM = z(2, B, Tkp), (z(2, B, Tkp) if self.lsa else None)
         self.HC, self.H0, self.H0d = z(2, B, 768), z(2, B, 256), _buf(B, 256, dev=dev)
         self.S0, self.S1 = z(2, B, 5, 256), z(2, B, 5, 256)
         self.H0[0].copy_(tape.h0[0])
-        self.xp0, self.ga, self.gb, self.tz, self.o = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev), _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+        W, CUM, HC, H0, S0, S1 = self.W, self.CUM, self.HC, self.H0, self.S0, self.S1
+        # where the cell's rows live at even and at odd positions (c = i & 1, p the other half); H0[c] = layer 0's h before position i
+        self.halves = [(HC[p, :, :256], W[p, :, :Tk], W[c, :, :Tk], CUM[p, :, :Tk] if self.lsa else None, CUM[c, :, :Tk] if self.lsa else None, HC[c, :, 256:],
+                        H0[c], H0[p], S0[c], S0[p, :, 4], S1[c], S1[p, :, 4], HC[c, :, :256]) for c, p in ((0, 1), (1, 0))]
+        self.xp0, self.tz, self.o = _buf(B, 1024, dev=dev), _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
         self.p_dec = float(tape.model.decoder.p)
         self.F1 = _drop_factor(self.p_dec, tape.seed, stream_drop, max_len * B, 256, dev).view(max_len, B, 256) if self.p_dec > 0.0 else None
         tape.site("g_drop0", self.p_dec, stream_drop, max_len * B, 256)
@@ -1043,26 +990,12 @@ class _GenState:
         self.running = torch.ones((), dtype=torch.int32, device=dev)
 
     def step(self, i, pre):
-        """RNNDecoder on position i from the prenet's rows pre [B,256] up to the projection (the train-mode step of _loop_forward, 8 launches);
+        """RNNDecoder on position i from the prenet's rows pre [B,256] up to the projection: xp0's row, the cell, the projection (9 launches);
         leaves [h1 | ctx] in HC[i & 1] and returns the projection's pre-activation [B,256]."""
-        t, P = self.tape, self.tape.P
-        Tk, cur, prv = t.Tk, i & 1, (i & 1) ^ 1
-        HC, H0, S0, S1, ga, gb = self.HC, self.H0, self.S0, self.S1, self.ga, self.gb
-        b_ih0, b_hh0, b_ih1, b_hh1 = P.bias
-        ops.rnn_linear(pre, P.w_ih0_p[0], b_ih0, self.xp0)
-        q = HC[prv, :, :256] if i else t.h0[1]                                              # the top layer's h from BEFORE this position's LSTM
-        ops.rnn_attn_step_train(P.mode, q, P.Wq, self.mem, P.v, t.enc, t.lens, HC[cur, :, 256:], self.W[cur, :, :Tk], prev_in=self.W[prv, :, :Tk],
-                                cum_in=self.CUM[prv, :, :Tk] if self.lsa else None, cum_out=self.CUM[cur, :, :Tk] if self.lsa else None, conv_w=P.conv_w,
-                                dense_w=P.dense_w)
-        ops.rnn_linear(HC[cur, :, 256:], P.w_ih0_c, None, gb, R=self.xp0)
-        ops.rnn_linear(H0[cur], P.w_hh0, b_hh0, ga, R=gb)                                   # H0[i & 1] = layer 0's h before position i
-        F1 = self.F1
-        h0_new = H0[prv]
-        ops.lstm_cell_train(ga, S0[prv, :, 4] if i else t.c0[0], S0[cur], h0_new, mask=F1[i] if F1 is not None else None, hd=self.H0d if F1 is not None else None)
-        ops.rnn_linear(self.H0d if F1 is not None else h0_new, P.w_ih1, b_ih1, gb)
-        ops.rnn_linear(q, P.w_hh1, b_hh1, ga, R=gb)
-        ops.lstm_cell_train(ga, S1[prv, :, 4] if i else t.c0[1], S1[cur], HC[cur, :, :256])
-        return ops.rnn_linear(HC[cur], P.proj[0][0], P.proj[1], self.tz)
+        P, F1 = self.tape.P, self.F1
+        ops.rnn_linear(pre, P.w_ih0_p[0], P.bias[0], self.xp0)
+        self.cell(i == 0, self.xp0, F1[i] if F1 is not None else None, self.H0d if F1 is not None else None, *self.halves[i & 1])
+        return ops.rnn_linear(self.HC[i & 1], P.proj[0][0], P.proj[1], self.tz)
 
 
 def _begin_generation(what, model, cls, pack_cls, enc_outputs, lens_k, max_len, seed):
@@ -1102,7 +1035,6 @@ def text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0):
     sequence's length, lens [B] int64)): T = max(lens) positions ran, a sequence that never drew EOS has length max_len.  The prenet's three
     BatchNorms take T momentum updates (num_batches_tracked += T); the model's cached eval operands are dropped."""
     from .network import TextRNN
-    from .utils import SOS_IDX, EOS_IDX
     what = "text_generate_train"
     tape, B, max_len = _begin_generation(what, model, TextRNN, TextDecoderPack, enc_outputs, lens_k, max_len, seed)
     P, dev = tape.P, tape.enc.device
@@ -1142,7 +1074,7 @@ def text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0):
         ops.prefix_gen_end_text(logits, P.V, tokens, i, st.stop_lens, max_len, EOS_IDX, st.running)
 
     steps = _run_positions(st, max_len, one)
-    model.__dict__.pop("_rnn_pack", None)                                                   # the running statistics moved under the cached eval operands
+    rnn.drop_eval_pack(model)
     host = torch.cat([st.stop_lens.view(B, 1), tokens[:, :steps]], 1).cpu()                 # the one read-back after the loop: lengths and tokens
     lens_host = [int(v) for v in host[:, 0]]
     T = max(lens_host)

@@ -30,6 +30,7 @@ import math
 import torch
 
 from . import ops, train_rnn
+from .rnn import PACK_SLOTS
 from .utils import is_deterministic, next_seed, specaugment
 
 _F32 = torch.float32
@@ -56,8 +57,8 @@ def _touched(model):
 def drop_cached_operands(model):
     """The optimizer's kernels write the parameters behind torch's version counters, on which the models' derived operands are keyed."""
     for m in (model.text_m, model.speech_m):
-        for key in ("_rnn_pack", "_rnn_train_pack", "_rnn_decoder_train_pack"):
-            m.__dict__.pop(key, None)
+        for slot in PACK_SLOTS:
+            m.__dict__.pop(slot, None)
 
 
 # ---- the optimizer ------------------------------------------------------------------------------------------------------------------------------

@@ -59,7 +59,7 @@ def _run_steps(graphed, use_disc, lr, n=6):
         stepper.flush(losses)
     join_streams()
     torch.cuda.synchronize()
-    return ({k: [float(x) for x in v] for k, v in losses.items()}, model._store().flat.detach().cpu().clone(), dict(opt._steps), opt.param_groups[0]["lr"])
+    return ({k: [float(x) for x in v] for k, v in losses.items()}, model._store().flat.detach().cpu().clone(), {s.name: s.step for s in opt.segments}, opt.param_groups[0]["lr"])
 
 
 @pytest.mark.parametrize("replay", ["streams", "hipgraph"])

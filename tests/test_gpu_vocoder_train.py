@@ -414,7 +414,8 @@ def test_flat_adamw_matches_fp64_torch(decoupled):
     assert topt.param_groups[0]["lr"] == 1e-3
     opt2 = FlatAdamW(make_model(sd), lr=0.5, decoupled=decoupled)
     opt2.load_state_dict(topt.state_dict())
-    assert opt2._step == 3 and opt2.param_groups[0]["lr"] == 1e-3 and torch.equal(opt2._m, opt._m) and torch.equal(opt2._v, opt._v)
+    seg, seg2 = opt.segments[0], opt2.segments[0]
+    assert seg2.step == 3 and opt2.param_groups[0]["lr"] == 1e-3 and torch.equal(seg2.m, seg.m) and torch.equal(seg2.v, seg.v)
     opt.zero_grad()
     assert all(bool((p.grad == 0).all()) for p in model.parameters())
 

@@ -18,14 +18,13 @@ Differences that are deliberate and MI355X-motivated:
   * cm_steps (back-translation) generates with a K/V-cached decoder (unast_amd/inference.py) instead of re-running the
     decoder over the growing prefix at every step.
 """
-import math
 import os
 from collections import defaultdict
 
 import torch
 import torch.nn as nn
 
-from . import ddp, functional as F, ops
+from . import ddp, flat_adam, functional as F, ops
 from .engine import Var, run_segment, on_stream, side_streams, join_streams, stream_of, join_wgrad_streams
 from .network import TextTransformer, SpeechTransformer, UNAST, Discriminator, LSTMDiscriminator, _as_padded
 from .utils import (PAD_IDX, SOS_IDX, EOS_IDX, lens_i32, specaugment, sent_lens_to_mask, get_teacher_ratio, is_deterministic,
@@ -941,29 +940,34 @@ def get_transformer_paper_schedule(optimizer, num_warmup_steps, last_epoch=-1):
     return torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda, last_epoch)
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """torch.optim.Adam(W) semantics (src/train.py:929-932) over the model's flat buffers: one sum-of-squares launch per
-    active range + one clip+AdamW launch per range.  Ranges without gradients in this phase (frozen discriminator in the
-    generator phase, generator under no_grad in the D phase, never-used reduce_c_W) are skipped entirely — the
-    `grad is None => skip` behaviour the reference relies on.  Works with torch LR schedulers (param_groups[0]['lr'])."""
+class FusedAdamW(flat_adam.FlatAdam):
+    """flat_adam.FlatAdam (src/train.py:929-932) over the model's FlatStore: the segments are the store's 'gen' and 'disc' regions.  Regions
+    without gradients in this phase (frozen discriminator in the generator phase, generator under no_grad in the D phase) are skipped
+    entirely -- the `grad is None => skip` behaviour the reference relies on; the never-used reduce_c_W lies outside both and keeps no state."""
 
     def __init__(self, model, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, decoupled=True):
         self.model = model
-        super().__init__(list(model.parameters()), dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps))
-        self.decoupled = decoupled
-        self._m = self._v = None
-        self._steps = defaultdict(int)
-        self._ss = None
-        self.last_grad_norm_sq = None
+        super().__init__(list(model.parameters()), [], lr, weight_decay, betas, eps, decoupled)
+        self._m = self._v = None         # store-wide moment buffers: a segment's moments are slices of them
+        self._by_range = {}              # gradient range -> its segment
         self._slots = {}                 # gradient range -> index of its hyper-parameter triple in ops.step_state()
         self.captured_ranges = []        # ranges stepped while a HIP graph was being captured, in order
 
     def _buffers(self, st):
         if self._m is None or self._m.device != st.flat.device or self._m.numel() != st.total:
-            self._m = torch.zeros_like(st.flat)
-            self._v = torch.zeros_like(st.flat)
+            self._m, self._v = torch.zeros_like(st.flat), torch.zeros_like(st.flat)
             self._ss_by_phase = {}
-            self._ss = torch.zeros(1, dtype=torch.float64, device=st.flat.device)
+            steps = {s.name: s.step for s in self.segments}
+            names = {id(p): n for n, p in st.params.items()}
+            self.segments = []
+            for r in ("gen", "disc"):
+                a, b = st.regions[r]
+                live = [(p, names[id(p)]) for p in self.param_groups[0]["params"] if a <= st.offsets[names[id(p)]] < b]
+                seg = flat_adam.Segment(r, [p for p, _ in live], [st.offsets[n] - a for _, n in live], st.flat[a:b], st.grad[a:b], st.flat_split[a:b],
+                                        self._m[a:b], self._v[a:b], [n.endswith(".conv.weight") for _, n in live])       # tap-major in HBM
+                seg.step = steps.get(r, 0)
+                self.segments.append(seg)
+            self._by_range = {st.regions[s.name]: s for s in self.segments}
 
     @torch.no_grad()
     def step(self, max_norm=0.0, closure=None, zero_grads=False):
@@ -975,32 +979,20 @@ class FusedAdamW(torch.optim.Optimizer):
         if not ranges:
             return
         ddp.finish(st, ranges)                 # waits for the buckets that travelled during the backward, reduces the rest
-        g = self.param_groups[0]
         key = tuple(ranges)                    # one norm scalar per phase: the D phase may run on its own stream
         ss = self._ss_by_phase.get(key)
         if ss is None:
             ss = self._ss_by_phase[key] = torch.zeros(1, dtype=torch.float64, device=st.flat.device)
         self._ss = ss
-        self._ss.zero_()
-        for a, b in ranges:
-            ops.sumsq(st.grad[a:b], self._ss)
-        self.last_grad_norm_sq = self._ss
-        capturing = torch.cuda.is_current_stream_capturing()
-        for a, b in ranges:
-            if capturing:
-                # Recorded into a HIP graph (unast_amd.graphed): the learning rate and the bias corrections are read from device
-                # memory at replay time; the host-side step count of this range advances per replay (replay_hyper).
-                slot = self._slots.setdefault((a, b), len(self._slots))
-                ops.adamw(st.flat[a:b], st.grad[a:b], self._m[a:b], self._v[a:b], self._ss, float(max_norm), 0.0,
-                          g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], 0, split_out=st.flat_split[a:b],
-                          decoupled=self.decoupled, dev_hyper=ops.hyper_slot(slot), zero_grad=zero_grads)
-                self.captured_ranges.append((a, b))
-                continue
-            self._steps[(a, b)] += 1
-            ops.adamw(st.flat[a:b], st.grad[a:b], self._m[a:b], self._v[a:b], self._ss, float(max_norm), float(g["lr"]),
-                      g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._steps[(a, b)], split_out=st.flat_split[a:b],
-                      decoupled=self.decoupled, zero_grad=zero_grads)
-        upd = [r for r, ab in st.regions.items() if ab in ranges]
+        hyper = None
+        if torch.cuda.is_current_stream_capturing():
+            # Recorded into a HIP graph (unast_amd.graphed): the learning rate and the bias corrections are read from device
+            # memory at replay time; the host-side step count of a range advances per replay (replay_hyper).
+            hyper = [ops.hyper_slot(self._slots.setdefault(r, len(self._slots))) for r in ranges]
+            self.captured_ranges += ranges
+        segs = [self._by_range[r] for r in ranges]
+        self._launch(segs, max_norm, hyper, zero_grads)
+        upd = [s.name for s in segs]
         if zero_grads:
             st.zeroed_by_step.update(upd)
         st.refresh_T(upd)                      # W^T copies of what was just updated
@@ -1009,69 +1001,21 @@ class FusedAdamW(torch.optim.Optimizer):
     def replay_hyper(self, rng, lr):
         """Host side of one replay of a captured step for the range `rng`: advances its step count and returns
         (slot, [lr, 1 - beta1^t, sqrt(1 - beta2^t)]) for the device block the captured AdamW launch reads."""
-        self._steps[rng] += 1
+        seg = self._by_range[rng]
+        seg.step += 1
         g = self.param_groups[0]
-        return self._slots[rng], ops.adam_hyper(lr, g["betas"][0], g["betas"][1], self._steps[rng])
+        return self._slots[rng], ops.adam_hyper(lr, g["betas"][0], g["betas"][1], seg.step)
 
     def zero_grad(self, set_to_none=True):
         self.model._store().zero_grad()
 
-    # ---- torch.optim.AdamW-compatible (de)serialisation (reference checkpoints: src/utils.py:139-195) ----------------
-    def _param_ranges(self, st):
-        """[(index, name, param, offset, numel, region_range)] in model.parameters() order (= torch's param indices)."""
-        out = []
-        names = {id(p): n for n, p in st.params.items()}
-        for i, p in enumerate(self.model.parameters()):
-            n = names[id(p)]
-            o = st.offsets[n]
-            rr = next((a, b) for (a, b) in st.regions.values() if a <= o < b)
-            out.append((i, n, p, o, p.numel(), rr))
-        return out
-
     def state_dict(self):
-        st = self.model._store()
-        self._buffers(st)
-        state = {}
-        for i, n, p, o, k, rr in self._param_ranges(st):
-            steps = self._steps.get(rr, 0)
-            if steps == 0:
-                continue                                   # never updated (e.g. reduce_c_W): torch keeps no state either
-            m, v = self._m[o:o + k], self._v[o:o + k]
-            if n.endswith(".conv.weight"):                 # tap-major in HBM -> reference [Cout,Cin,5]
-                co, ci, ks = p.shape
-                m, v = m.view(co, ks, ci).permute(0, 2, 1), v.view(co, ks, ci).permute(0, 2, 1)
-            else:
-                m, v = m.view(p.shape), v.view(p.shape)
-            state[i] = {"step": torch.tensor(float(steps)), "exp_avg": m.detach().cpu().contiguous(), "exp_avg_sq": v.detach().cpu().contiguous()}
-        g = dict(self.param_groups[0])
-        g["params"] = list(range(len(list(self.model.parameters()))))
-        for key, val in (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False), ("differentiable", False), ("fused", None)):
-            g.setdefault(key, val)
-        return {"state": state, "param_groups": [g]}
+        self._buffers(self.model._store())
+        return super().state_dict()
 
     def load_state_dict(self, sd):
-        st = self.model._store()
-        self._buffers(st)
-        self._m.zero_(); self._v.zero_()
-        self._steps = defaultdict(int)
-        for i, n, p, o, k, rr in self._param_ranges(st):
-            ent = sd["state"].get(i, sd["state"].get(str(i)))
-            if ent is None:
-                continue
-            m, v = ent["exp_avg"].to(self._m.device, torch.float32), ent["exp_avg_sq"].to(self._m.device, torch.float32)
-            if n.endswith(".conv.weight"):
-                m, v = m.permute(0, 2, 1), v.permute(0, 2, 1)
-            self._m[o:o + k].copy_(m.reshape(-1))
-            self._v[o:o + k].copy_(v.reshape(-1))
-            self._steps[rr] = max(self._steps[rr], int(float(ent["step"])))
-        g = sd["param_groups"][0]
-        for key in ("lr", "weight_decay", "betas", "eps", "initial_lr"):
-            if key in g:
-                self.param_groups[0][key] = tuple(g[key]) if key == "betas" else g[key]
-
-    def grad_norm(self):
-        """Pre-clip global gradient norm of the last step (one host read; for logging/tests)."""
-        return math.sqrt(float(self.last_grad_norm_sq.item()))
+        self._buffers(self.model._store())
+        super().load_state_dict(sd)
 
 
 def allreduce_grads(st, ranges, scale_fn=None):

@@ -13,10 +13,11 @@ after it starts from zero.
 
 Where what lives.  The discriminator keeps living in the model's FlatStore (UNAST._store() of an RNN model covers the discriminator alone:
 its kernels address its LSTM weights as spans of that buffer); the optimizer takes the store's 'disc' region as one more segment next to
-its own two -- flat parameter and gradient buffers for text_m and for speech_m with p.data / p.grad as views (train_vocoder.FlatAdamW's
-scheme; train_rnn._prepare_grads keeps such a .grad in place).  A segment whose gradients were not produced since the last zero_grad is
-skipped entirely -- no decay, no moment update, no step count, no share in the clip norm: torch.optim's `grad is None`.  'Produced' is
-tracked on the host (model._rnn_touched, FlatStore.touched).
+its own two -- flat parameter and gradient buffers for text_m and for speech_m with p.data / p.grad as views (flat_adam.adopt;
+train_rnn._prepare_grads keeps such a .grad in place).  Segments, launch sequence and (de)serialisation are unast_amd.flat_adam's, shared with
+the transformer's and the vocoder's optimizers; this module decides which segments step.  A segment whose gradients were not produced since
+the last zero_grad is skipped entirely -- no decay, no moment update, no step count, no share in the clip norm: torch.optim's
+`grad is None`.  'Produced' is tracked on the host (model._rnn_touched, FlatStore.touched).
 
 The cross-model (back-translation) step is train_cm_step below, and train_step here is the step with cm_steps >= 0: both are explicit
 entry points of this module.  unast_amd.train's own train_cm_step / crossmodel_step / train(args) with cm_steps > 0 keep raising CM_REASON for
@@ -25,11 +26,9 @@ model_type='rnn' (flipping that dispatch is a follow-up).
 Out of scope (raise NotImplementedError): evaluate(), graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step /
 crossmodel_step called directly (they would have to return autograd-connected losses).
 """
-import math
-
 import torch
 
-from . import ops, train_rnn
+from . import flat_adam, ops, train_rnn
 from .rnn import PACK_SLOTS
 from .utils import is_deterministic, next_seed, specaugment
 
@@ -62,48 +61,18 @@ def drop_cached_operands(model):
 
 
 # ---- the optimizer ------------------------------------------------------------------------------------------------------------------------------
-class _Segment:
-    """One range the optimizer steps or skips as a whole: flat parameters, gradients, both moments, a step count."""
-
-    def __init__(self, name, params, offsets, flat, grad, split=None):
-        self.name, self.params, self.offsets, self.flat, self.grad, self.split = name, params, offsets, flat, grad, split
-        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.step = 0
-
-
-def _own_segment(name, params):
-    """Flat buffers of this optimizer's own: every parameter at a 16-byte boundary, zero padding between; p.data and p.grad become views."""
-    offsets, total = [], 0
-    for p in params:
-        offsets.append(total)
-        total += (p.numel() + 3) // 4 * 4
-    dev = params[0].device
-    flat, grad = torch.zeros(total, dtype=_F32, device=dev), torch.zeros(total, dtype=_F32, device=dev)
-    with torch.no_grad():
-        for p, o in zip(params, offsets):
-            view = flat[o:o + p.numel()].view(p.shape)
-            view.copy_(p)
-            p.data = view
-            p.grad = grad[o:o + p.numel()].view(p.shape)
-    return _Segment(name, params, offsets, flat, grad)
-
-
-class RNNFlatAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW (decoupled=True) or torch.optim.Adam with L2 weight decay (decoupled=False) over UNAST(TextRNN, SpeechRNN[, D]) with
-    clip_grad_norm_ folded in, on the kernels train.FusedAdamW uses: one unast_sumsq and one unast_adamw launch per segment that has
-    gradients.  Segments: text_m, speech_m (this optimizer's flat buffers) and the discriminator (the 'disc' region of the model's FlatStore on
-    the GPU; laid out like the other two on a CPU / meta model, where only state_dict() and load_state_dict() work).  state_dict() and
-    load_state_dict() speak torch.optim.AdamW's format, parameters indexed in model.parameters() order."""
+class RNNFlatAdamW(flat_adam.FlatAdam):
+    """flat_adam.FlatAdam over UNAST(TextRNN, SpeechRNN[, D]): one unast_sumsq and one unast_adamw launch per segment that has gradients.
+    Segments: text_m, speech_m (flat buffers this optimizer adopts the parameters into) and the discriminator (the 'disc' region of the model's
+    FlatStore on the GPU; adopted like the other two on a CPU / meta model, where only state_dict() and load_state_dict() work)."""
 
     def __init__(self, model, lr, weight_decay=0.0, decoupled=True, betas=(0.9, 0.999), eps=1e-8):
         params = list(model.parameters())
         if not params or any(p.dtype is not _F32 for p in params):
             raise ValueError("RNNFlatAdamW: float32 parameters")
-        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps))
-        self.model, self.decoupled = model, bool(decoupled)
-        self.segments = [_own_segment(n, list(getattr(model, n).parameters())) for n in GEN_SEGMENTS]
+        segments = [flat_adam.adopt(n, list(getattr(model, n).parameters())) for n in GEN_SEGMENTS]
         disc = model.discriminator
-        self._store = None
+        self.model, self._store = model, None
         if disc is not None:
             dparams = list(disc.parameters())
             if dparams[0].is_cuda:
@@ -111,11 +80,10 @@ class RNNFlatAdamW(torch.optim.Optimizer):
                 a, b = st.regions["disc"]
                 names = {id(p): n for n, p in st.params.items()}
                 live = [p for p in dparams if a <= st.offsets[names[id(p)]] < b]                   # (reduce_c_W sits in 'disc_unused': never has a gradient)
-                self.segments.append(_Segment("disc", live, [st.offsets[names[id(p)]] - a for p in live], st.flat[a:b], st.grad[a:b], st.flat_split[a:b]))
+                segments.append(flat_adam.Segment("disc", live, [st.offsets[names[id(p)]] - a for p in live], st.flat[a:b], st.grad[a:b], st.flat_split[a:b]))
             else:
-                self.segments.append(_own_segment("disc", dparams))
-        dev = params[0].device
-        self._ss = torch.zeros(1, dtype=torch.float64, device=dev)
+                segments.append(flat_adam.adopt("disc", dparams))
+        super().__init__(params, segments, lr, weight_decay, betas, eps, decoupled)
         self.last_stepped = []
         drop_cached_operands(model)
 
@@ -140,16 +108,10 @@ class RNNFlatAdamW(torch.optim.Optimizer):
         self.last_stepped = [s.name for s in segs]
         if not segs:
             return
-        g = self.param_groups[0]
-        self._ss.zero_()
         for s in segs:
             if s.name != "disc":
                 self._adopt_grads(s)
-            ops.sumsq(s.grad, self._ss)
-        for s in segs:
-            s.step += 1
-            ops.adamw(s.flat, s.grad, s.m, s.v, self._ss, float(max_norm), float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], s.step,
-                      split_out=s.split, decoupled=self.decoupled)
+        self._launch(segs, max_norm)
         if self._store is not None and "disc" in self.last_stepped:
             self._store.refresh_T(["disc"])                # W^T copies and tiled bf16 planes of what was just updated (train.FusedAdamW.step)
             self._store.refresh_planes(["disc"])
@@ -165,46 +127,6 @@ class RNNFlatAdamW(torch.optim.Optimizer):
         touched.clear()
         if self._store is not None:
             self._store.zero_grad()
-
-    def grad_norm(self):
-        """Pre-clip global gradient norm of the last step (one host read; for logging and tests)."""
-        return math.sqrt(float(self._ss.item()))
-
-    def _entries(self):
-        """[(torch's parameter index, segment, offset, parameter)] for every parameter a segment holds."""
-        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
-        return [(index[id(p)], s, o, p) for s in self.segments for p, o in zip(s.params, s.offsets)]
-
-    def state_dict(self):
-        state = {}
-        for i, s, o, p in sorted(self._entries(), key=lambda e: e[0]):
-            if s.step == 0:
-                continue                                   # never stepped: torch keeps no state either
-            k = p.numel()
-            state[i] = {"step": torch.tensor(float(s.step)), "exp_avg": s.m[o:o + k].view(p.shape).detach().cpu().clone(),
-                        "exp_avg_sq": s.v[o:o + k].view(p.shape).detach().cpu().clone()}
-        g = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        g["params"] = list(range(len(self.param_groups[0]["params"])))
-        for key, val in (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False), ("differentiable", False), ("fused", None)):
-            g.setdefault(key, val)
-        return {"state": state, "param_groups": [g]}
-
-    def load_state_dict(self, sd):
-        for s in self.segments:
-            s.m.zero_(); s.v.zero_()
-            s.step = 0
-        for i, s, o, p in self._entries():
-            ent = sd["state"].get(i, sd["state"].get(str(i)))
-            if ent is None:
-                continue
-            k = p.numel()
-            s.m[o:o + k].copy_(ent["exp_avg"].to(s.m.device, _F32).reshape(-1))
-            s.v[o:o + k].copy_(ent["exp_avg_sq"].to(s.m.device, _F32).reshape(-1))
-            s.step = max(s.step, int(float(ent["step"])))
-        g = sd["param_groups"][0]
-        for key in ("lr", "weight_decay", "betas", "eps", "initial_lr"):
-            if key in g:
-                self.param_groups[0][key] = tuple(g[key]) if key == "betas" else g[key]
 
 
 _MODEL_KEYS = ("hidden", "e_in", "t_emb_dim", "s_pre_hid", "num_layers", "e_bi", "d_attn", "attn_dim", "num_mels")      # what network._rnn_check_args reads

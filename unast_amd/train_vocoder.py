@@ -8,7 +8,7 @@ forward stored, never recomputed.  Everything is enqueued on the current stream;
 """
 import torch
 
-from . import ops
+from . import flat_adam, ops
 from .vocoder import Vocoder
 
 _F32 = torch.float32
@@ -264,34 +264,16 @@ def valid_loss(model, mel, mag, loss_type="l1"):
     return loss
 
 
-class FlatAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW (decoupled=True) or torch.optim.Adam with L2 weight decay (decoupled=False) over the vocoder's parameters
-    (src/train_vocoder.py:31-35), with clip_grad_norm_ folded in: parameters and gradients are re-pointed to views of two flat fp32 buffers
-    (each parameter at a 16-byte boundary, zero padding between), and step(max_norm) is one ops.sumsq launch and one ops.adamw launch --
-    the kernels train.FusedAdamW uses.  state_dict() / load_state_dict() speak torch.optim.AdamW's format."""
+class FlatAdamW(flat_adam.FlatAdam):
+    """flat_adam.FlatAdam over the vocoder's parameters (src/train_vocoder.py:31-35): parameters and gradients are re-pointed to views of two
+    flat fp32 buffers, one segment that is always stepped, so step(max_norm) is one ops.sumsq launch and one ops.adamw launch."""
 
     def __init__(self, model, lr, weight_decay=0.0, decoupled=True, betas=(0.9, 0.999), eps=1e-8):
         params = list(model.parameters())
         if not params or any(p.dtype is not _F32 or not p.is_cuda for p in params):
             raise ValueError("FlatAdamW: float32 CUDA parameters")
-        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps))
-        self.model, self.decoupled = model, bool(decoupled)
-        self._offsets, total = [], 0
-        for p in params:
-            self._offsets.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        dev = params[0].device
-        self.flat = torch.zeros(total, dtype=_F32, device=dev)
-        self.grad = torch.zeros(total, dtype=_F32, device=dev)
-        self._m, self._v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self._ss = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._step = 0
-        with torch.no_grad():
-            for p, o in zip(params, self._offsets):
-                view = self.flat[o:o + p.numel()].view(p.shape)
-                view.copy_(p)
-                p.data = view
-                p.grad = self.grad[o:o + p.numel()].view(p.shape)
+        self.model = model
+        super().__init__(params, [flat_adam.adopt("vocoder", params)], lr, weight_decay, betas, eps, decoupled)
         self._touch()
 
     def _touch(self):
@@ -301,51 +283,11 @@ class FlatAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, max_norm=0.0, closure=None):
-        g = self.param_groups[0]
-        self._ss.zero_()
-        ops.sumsq(self.grad, self._ss)
-        self._step += 1
-        ops.adamw(self.flat, self.grad, self._m, self._v, self._ss, float(max_norm), float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"],
-                  g["weight_decay"], self._step, decoupled=self.decoupled)
+        self._launch(self.segments, max_norm)
         self._touch()
 
     def zero_grad(self, set_to_none=False):
-        self.grad.zero_()
-
-    def grad_norm(self):
-        """Pre-clip global gradient norm of the last step (one host read)."""
-        return float(self._ss.item()) ** 0.5
-
-    def state_dict(self):
-        state = {}
-        params = self.param_groups[0]["params"]
-        if self._step > 0:
-            for i, (p, o) in enumerate(zip(params, self._offsets)):
-                k = p.numel()
-                state[i] = {"step": torch.tensor(float(self._step)), "exp_avg": self._m[o:o + k].view(p.shape).detach().cpu().clone(),
-                            "exp_avg_sq": self._v[o:o + k].view(p.shape).detach().cpu().clone()}
-        g = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        g["params"] = list(range(len(params)))
-        for key, val in (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False), ("differentiable", False), ("fused", None)):
-            g.setdefault(key, val)
-        return {"state": state, "param_groups": [g]}
-
-    def load_state_dict(self, sd):
-        self._m.zero_(); self._v.zero_()
-        self._step = 0
-        params = self.param_groups[0]["params"]
-        for i, (p, o) in enumerate(zip(params, self._offsets)):
-            ent = sd["state"].get(i, sd["state"].get(str(i)))
-            if ent is None:
-                continue
-            k = p.numel()
-            self._m[o:o + k].copy_(ent["exp_avg"].to(self._m.device, _F32).reshape(-1))
-            self._v[o:o + k].copy_(ent["exp_avg_sq"].to(self._m.device, _F32).reshape(-1))
-            self._step = max(self._step, int(float(ent["step"])))
-        g = sd["param_groups"][0]
-        for key in ("lr", "weight_decay", "betas", "eps", "initial_lr"):
-            if key in g:
-                self.param_groups[0][key] = tuple(g[key]) if key == "betas" else g[key]
+        self.segments[0].grad.zero_()
 
 
 def initialize(args):

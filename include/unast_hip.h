@@ -590,6 +590,20 @@ int unast_layernorm_partials_finalize(const float* part, int nblk, int C, float*
  * replay; stands where the reference's Python passes lr / step to torch.optim (src/train.py:361, 654-655). */
 int unast_set_words(unsigned int* dst, const unsigned int* host_words, int n, hipStream_t stream);
 
+/* compute_per's distance on the device (csrc/metrics.hip; src/utils.py:24-34: jiwer 2.2.0 flattens both sentence lists into one word list each
+ * and takes wer = Levenshtein(truth, hypothesis) / len(truth) over them).  ref int64 [B,Tr] (row stride ld_ref), hyp int64 [B,Th] (row stride
+ * ld_hyp), ref_len / hyp_len int32 [B] (clamped to 0..T; 0 is legal); flat(x) = each row's first len[b] ids in batch order -- nothing at or
+ * behind len[b] is read.  out2 int32 [2] = {Levenshtein(flat(ref), flat(hyp)) with unit costs and ids compared as full int64, len(flat(ref))}.
+ * One launch of one workgroup: the shorter flattened sequence on the DP's columns, a chunk of consecutive columns per thread in registers, the
+ * other walked row by row; no atomics, the same bits every run.  Limit: min(B*Tr, B*Th) <= threads x chunk = 1024 x 64 (unast_edit_distance_limits
+ * writes the two factors), checked before any launch; the longer side only has to stay below 2^30 ids.  chunk: 0 lets the kernel take the
+ * smallest power of two that covers the columns; a larger power of two (up to 64) forces that many columns per thread (tests reach every
+ * chunk size at small shapes with it).  ws: unast_edit_distance_ws_bytes(B, Tr, Th) bytes, 8-byte aligned, receives the flattened sequences. */
+int unast_edit_distance_limits(int* out2);
+int64_t unast_edit_distance_ws_bytes(int B, int Tr, int Th);
+int unast_edit_distance(const int64_t* ref, int64_t ld_ref, const int* ref_len, int Tr, const int64_t* hyp, int64_t ld_hyp,
+                        const int* hyp_len, int Th, int B, int chunk, void* ws, int64_t ws_bytes, int* out2, hipStream_t stream);
+
 /* Stream replay of a captured HIP graph (csrc/graph_exec.cpp): the nodes of `graph` (a hipGraph_t, e.g. torch.cuda.CUDAGraph's
  * raw handle of the captured train step -- the reference has no counterpart: it launches src/train.py:602-655 op by op) are laid out
  * on `nstreams` ordinary streams with events on the cross-stream edges and re-issued with hipLaunchKernel / hipMemsetAsync /

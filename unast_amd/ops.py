@@ -1336,11 +1336,11 @@ def conv_taps_fwd(x3d, Wp, bias, out, pad_left, act=0, R=None):
     slice): out[b,t] = epi(sum_j Wp[:,j,:] x[b, t + j - pad_left]), zero outside each sequence; epi = + bias -> relu if act -> + R."""
     B, T, Cin = x3d.shape
     Cout, taps, _ = Wp.shape
-    if not (Wp.is_contiguous() and Wp.shape[2] == Cin and x3d.stride(2) == 1 and out.stride(2) == 1 and x3d.stride(0) == T * x3d.stride(1)
-            and out.stride(0) == T * out.stride(1) and out.shape == (B, T, Cout)):
+    dense = lambda t: B == 1 or t.stride(0) == T * t.stride(1)              # noqa: E731  (a single sequence has no batch stride to speak of)
+    if not (Wp.is_contiguous() and Wp.shape[2] == Cin and x3d.stride(2) == 1 and out.stride(2) == 1 and dense(x3d) and dense(out) and out.shape == (B, T, Cout)):
         raise ValueError("conv_taps_fwd: tap-major contiguous weights and [B,T,C] operands with dense batch strides")
     if (bias is not None and bias.numel() != Cout) or (R is not None and not (R.shape[-1] == Cout and R.numel() == B * T * Cout and R.stride(-1) == 1
-                                                                         and (R.dim() == 2 or R.stride(0) == T * R.stride(1)))):
+                                                                         and (R.dim() == 2 or dense(R)))):
         raise ValueError("conv_taps_fwd: bias [Cout]; R [B*T, Cout] or [B,T,Cout] with dense batch strides")
     if x3d.dtype is not _F32 or Wp.dtype is not _F32 or out.dtype is not _F32 or not out.is_cuda:
         for t, n in ((x3d, "x"), (Wp, "W"), (out, "out"), (bias, "bias"), (R, "R")):
@@ -1520,6 +1520,51 @@ def conv_taps_wgrad(dy3d, x3d, dWp, pad_left, db=None):
     check(lib().unast_conv_wgrad(config.NSPLIT, _p(dy3d), dy3d.stride(1), _p(x3d), x3d.stride(1), _p(dWp), B, T, Cin, Cout, taps, pad_left,
                                  _p(db), sk, _p(ws), ws_n, _stream()), "unast_conv_wgrad")
     return dWp
+
+
+# ---- evaluation metrics (csrc/metrics.hip) -----------------------------------------------------------------
+EDIT_THREADS, EDIT_CHUNK = 1024, 64                 # threads of the kernel's one workgroup, columns per thread chunk at most (the kernel's own: edit_distance_limits)
+EDIT_MAX_COLS = EDIT_THREADS * EDIT_CHUNK           # ids the shorter side may hold (B * T)
+
+
+def edit_distance_limits():
+    out = (_ct.c_int * 2)()
+    check(lib().unast_edit_distance_limits(_ct.addressof(out)), "unast_edit_distance_limits")
+    return out[0], out[1]
+
+
+def _ids_and_lens(name, ids, lens):
+    if not (torch.is_tensor(ids) and ids.is_cuda and ids.dtype == torch.int64 and ids.dim() == 2):
+        raise TypeError("edit_distance: %s must be an int64 CUDA tensor [B, T] (got %s)" % (name, (ids.dtype, tuple(ids.shape), str(ids.device)) if torch.is_tensor(ids) else type(ids)))
+    if not (torch.is_tensor(lens) and lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and tuple(lens.shape) == (ids.shape[0],)):
+        raise TypeError("edit_distance: %s_len must be a contiguous int32 CUDA tensor [B]" % name)
+    if ids.shape[1] > 1 and ids.stride(1) != 1 or ids.shape[0] > 1 and ids.stride(0) < ids.shape[1]:
+        raise ValueError("edit_distance: %s needs unit column stride and a row stride of at least T" % name)
+
+
+def edit_distance(ref, ref_len, hyp, hyp_len, out=None, ws=None, chunk=0):
+    """out int32 [2] = {Levenshtein(flat(ref), flat(hyp)), len(flat(ref))} on the device; flat = each row's first len[b] ids in batch order.
+    Raises ValueError before any launch when the shorter side could hold more than EDIT_MAX_COLS ids (min(B Tr, B Th))."""
+    _ids_and_lens("ref", ref, ref_len)
+    _ids_and_lens("hyp", hyp, hyp_len)
+    B, Tr = ref.shape
+    Th = hyp.shape[1]
+    if hyp.shape[0] != B or B < 1:
+        raise ValueError("edit_distance: ref and hyp need the same batch size >= 1 (got %d, %d)" % (B, hyp.shape[0]))
+    if min(B * Tr, B * Th) > EDIT_MAX_COLS:
+        raise ValueError("edit_distance: the shorter side holds up to %d ids; the kernel's limit is %d x %d" % (min(B * Tr, B * Th), EDIT_THREADS, EDIT_CHUNK))
+    need = int(lib().unast_edit_distance_ws_bytes(B, Tr, Th))
+    if ws is None:
+        ws = torch.empty(max(need // 8, 1), dtype=torch.int64, device=ref.device)
+    elif not (ws.is_cuda and ws.is_contiguous() and ws.numel() * ws.element_size() >= need):
+        raise ValueError("edit_distance: the workspace needs %d bytes" % need)
+    if out is None:
+        out = torch.empty(2, dtype=torch.int32, device=ref.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == 2):
+        raise TypeError("edit_distance: out must be a contiguous int32 CUDA tensor [2]")
+    check(lib().unast_edit_distance(_p(ref), ref.stride(0) if B > 1 else max(Tr, 1), _p(ref_len), Tr, _p(hyp), hyp.stride(0) if B > 1 else max(Th, 1), _p(hyp_len), Th, B,
+                                    int(chunk), _p(ws), ws.numel() * ws.element_size(), _p(out), _stream()), "unast_edit_distance")
+    return out
 
 
 # ---- optimizer ---------------------------------------------------------------------------------------------

@@ -198,21 +198,32 @@ def _conv(x3d, Wp, b, pad_left, out=None, work=None):
 
 
 # ---- encoders ---------------------------------------------------------------------------------------------------------------------------
-def text_frontend(P, text):
-    """TextPrenet over whole sequences (src/module.py:217-230, eval): embedding, three conv + BatchNorm + ReLU stages.  [B,T] -> [B,T,256]."""
+def text_frontend(P, text, noise=None):
+    """TextPrenet over whole sequences (src/module.py:217-230, eval): embedding, three conv + BatchNorm + ReLU stages.  [B,T] -> [B,T,256].
+    noise = (p, seed, stream): noise_fn on the embedded ids (src/network.py:519-521; it does not look at model.training, so evaluate() keeps it:
+    unast_amd.eval_rnn); None changes nothing."""
     B, T = text.shape
     x = _buf(B * T, P.emb.shape[1], dev=text.device)
-    ops.embed_fwd(text, P.emb, x, T)
+    if noise is None:
+        ops.embed_fwd(text, P.emb, x, T)
+    else:
+        ops.embed_fwd(text, P.emb, x, T, seed=noise[1], noise_p=noise[0], noise_stream=noise[2])
     x = x.view(B, T, -1)
     for wp, b in P.convs:
         x = _relu_(_conv(x, wp, b, 2))
     return x
 
 
-def speech_frontend(P, mel):
-    """SpeechPrenet (src/module.py:95-110, eval): two linear + ReLU layers per frame."""
+def speech_frontend(P, mel, noise=None):
+    """SpeechPrenet (src/module.py:95-110, eval): two linear + ReLU layers per frame.  noise = (p, seed, stream): noise_fn on the input mel
+    (src/network.py:306-307), as text_frontend's; None changes nothing."""
     B, T, M = mel.shape
-    h = _linear_rows(mel.reshape(B * T, M), P.fc1_rows, P.fc1[1], act=1)
+    m2 = mel.reshape(B * T, M)
+    if noise is not None:
+        mn = torch.empty_like(m2)
+        ops.rowmask(m2.contiguous(), mn, noise[0], noise[1], noise[2])
+        m2 = mn
+    h = _linear_rows(m2, P.fc1_rows, P.fc1[1], act=1)
     return _linear_rows(h, P.fc2_rows, P.fc2[1], act=1).view(B, T, -1)
 
 

@@ -23,8 +23,8 @@ The cross-model (back-translation) step is train_cm_step below, and train_step h
 entry points of this module.  unast_amd.train's own train_cm_step / crossmodel_step / train(args) with cm_steps > 0 keep raising CM_REASON for
 model_type='rnn' (flipping that dispatch is a follow-up).
 
-Out of scope (raise NotImplementedError): evaluate(), graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step /
-crossmodel_step called directly (they would have to return autograd-connected losses).
+Out of scope (raise NotImplementedError): graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step /
+crossmodel_step called directly (they would have to return autograd-connected losses).  evaluate() lives in unast_amd.eval_rnn.
 """
 import torch
 

@@ -146,6 +146,20 @@ def compute_per(ground_truth, hypothesis, ground_truth_lengths, hypothesis_lengt
     return edit_distance(ref, hyp) / float(len(ref))
 
 
+def compute_per_device(ground_truth, hypothesis, gt_lens, hyp_lens):
+    """compute_per of device tensors without bringing the ids to the host: ground_truth / hypothesis int64 [B,T] CUDA tensors, gt_lens / hyp_lens
+    [B] CUDA tensors.  The distance and the truth's length come from ops.edit_distance (csrc/metrics.hip) in one 8-byte read-back; the
+    division is Python's, so the value equals compute_per's exactly."""
+    for name, t in (("ground_truth", ground_truth), ("hypothesis", hypothesis), ("gt_lens", gt_lens), ("hyp_lens", hyp_lens)):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise TypeError("compute_per_device: %s must be a CUDA tensor (compute_per takes host data)" % name)
+    out = ops.edit_distance(ground_truth, lens_i32(gt_lens).contiguous(), hypothesis, lens_i32(hyp_lens).contiguous())
+    dist, n = out.tolist()
+    if n == 0:
+        raise ValueError("compute_per: empty ground truth")
+    return dist / float(n)
+
+
 def _to_lists(t):
     return t.detach().cpu().tolist() if torch.is_tensor(t) else np.asarray(t).tolist()
 

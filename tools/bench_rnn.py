@@ -12,7 +12,8 @@ text_decoder_forward, forward + backward, the prefix prenet's share, the loops' 
 saved bytes, and the prefix prenet issued position by position through the uniform-[B,T] entry points as the comparator of the slab form.
 --train-step: the whole train step of the family (unast_amd.train_rnn_step through unast_amd.train's entry points, dropout, noise, SpecAugment
 and the drawn permutation on) at T_text = 180, T_mel = 800, B in {4, 16}, both attention types -- ms per AE / SP / D sub-step and per
-optimizer step of each phase, one warm-up round and medians of 5.
+optimizer step of each phase, one warm-up round and medians of 5.  With --ddp the same under a process group of one forced rank (nccl backend,
+UNAST_DDP_FORCE=1): the optimizer steps then include the data-parallel exchange of their segments.
 --train-cm: the cross-model sub-step (unast_amd.train_rnn_step.train_cm_step) at T_text = 180, T_mel = 800, B in {4, 16}, both attention
 types, dropout on, one warm-up and medians of 5.  Generation length depends on the weights, so the stop rule is OFF here (the EOS and stop
 biases are set so that no sequence stops) and both generations run a fixed position count: 180 text positions, 800 frames.  Reports the text
@@ -20,7 +21,7 @@ prenet per position, fused (csrc/prefix_gen.hip: 4 launches) against the compara
 the three-launch conv with its operand split, train-mode unast_bn_fwd: 23 device operations), averaged over the prefixes L = 1..180, and the
 fused form at single prefix lengths L = 1 / 60 / 180 / 300 (its loaders reduce every tile's partial sums again: O(tiles^2) per launch); text and
 speech generation per position; and the whole sub-step.
-Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder | --train-step | --train-cm]"""
+Usage: python tools/bench_rnn.py [--reps 7] [--frames 800] [--train | --train-decoder | --train-text-decoder | --train-step [--ddp] | --train-cm]"""
 import argparse
 import os
 import statistics
@@ -29,6 +30,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if "--ddp" in sys.argv:
+    os.environ.setdefault("UNAST_DDP_FORCE", "1")          # read when unast_amd.ddp is imported: one rank takes the collective path
 from tests import rnn_weights  # noqa: E402
 from unast_amd import ops, rnn  # noqa: E402
 from unast_amd.inference import _capture  # noqa: E402
@@ -43,6 +46,7 @@ ap.add_argument("--train-decoder", action="store_true")
 ap.add_argument("--train-text-decoder", action="store_true")
 ap.add_argument("--train-step", action="store_true")
 ap.add_argument("--train-cm", action="store_true")
+ap.add_argument("--ddp", action="store_true")
 a = ap.parse_args()
 D = torch.device("cuda:0")
 B, TT, TM = 32, 180, 800
@@ -277,6 +281,15 @@ def train_step_mode():
     from types import SimpleNamespace
     from unast_amd import train
     train.DEVICE = D
+    if a.ddp:
+        import torch.distributed as dist
+        from unast_amd import ddp
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29617")
+        dist.init_process_group("nccl", rank=0, world_size=1)
+        torch.cuda.set_device(D)
+        print("--ddp: one forced rank over the nccl backend; data-parallel exchange active: %s; native communicator: %s"
+              % (ddp.active(), bool(ddp.native_comm())), flush=True)
     cfgs = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "rnn_configs.json")))
     for attn in ("luong", "lsa"):
         for Bb in (4, 16):
@@ -310,6 +323,9 @@ def train_step_mode():
             print("[%s] B=%d T_text=%d T_mel=%d: AE sub-step %.1f ms, SP sub-step %.1f ms, generator optimizer_step %.2f ms, D sub-step %.1f ms, "
                   "discriminator optimizer_step %.2f ms (the batch's upload included in the sub-steps)"
                   % (attn, Bb, TT, TM, med["ae"], med["sp"], med["opt_gen"], med["d"], med["opt_disc"]), flush=True)
+    if a.ddp:
+        print("collectives issued through the native communicator: %d" % ddp._Native.issued)
+        dist.destroy_process_group()
 
 
 def train_cm_mode():

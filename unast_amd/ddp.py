@@ -18,6 +18,10 @@ only then computes the global norm: the reference's order (generator update befo
 
 Every rank runs the same Python and the same autograd graph, so buckets become ready -- and collectives are issued -- in the
 same order on all ranks.
+
+The RNN family (unast_amd.train_rnn_step) keeps its generators' gradients outside the FlatStore, in the flat buffers of its optimizer's
+segments, and exchanges them without buckets or overlap: finish_segments() below, one blocking collective per segment inside the optimizer
+step, through the same _issue.
 """
 import os
 
@@ -205,13 +209,14 @@ def segment_backward(bucket, store):
         rng = bucket_ranges(store).get(bk)
         if rng is None or "gen" not in store.touched or any(r == rng for r in _State.issued):
             continue
-        _issue(store, bk, rng, overlap=True)
+        _issue(store.grad[rng[0]:rng[1]], bk, rng, overlap=True)
 
 
-def _issue(store, label, rng, overlap):
+def _issue(buf, label, rng, overlap):
+    """One all-reduce (sum) of the flat float32 buffer `buf`, logged as (label, a, b) with rng = (a, b): a range of the FlatStore's gradient
+    buffer for the transformer's callers (buf = store.grad[a:b]), (0, numel) of a segment's own buffer for finish_segments."""
     dist = _dist()
     a, b = rng
-    buf = store.grad[a:b]
     h = native_comm() if buf.is_cuda else 0
     if h:
         # RCCL through the C ABI: stream-ordered behind `s`; while a HIP graph is being captured a marker node stands in for the call and
@@ -292,7 +297,7 @@ def finish(store, ranges):
     n = 0
     for rng in ranges:
         for part in _subtract(rng, _State.issued):
-            _issue(store, "rest", part, overlap=False)
+            _issue(store.grad[part[0]:part[1]], "rest", part, overlap=False)
             n += 1
     for work in _State.pending:
         if isinstance(work, torch.cuda.Event):
@@ -305,3 +310,23 @@ def finish(store, ranges):
         scale(store.grad[a:b], 1.0 / ws)
     _State.issued, _State.pending = [], []
     return n
+
+
+def finish_segments(bufs, labels=None):
+    """Optimizer-step side for gradients that live outside a FlatStore (the flat_adam.Segment.grad buffers of the RNN family): one
+    blocking all-reduce per buffer on the current stream, in list order, then every buffer scaled by 1/world.  Nothing is pre-issued for
+    these callers and nothing overlaps: same transport choice, event chain and log as finish().  Returns the number of collectives issued
+    (0 when not distributed)."""
+    disarm()
+    if not active():
+        _State.issued, _State.pending = [], []
+        return 0
+    labels = list(labels) if labels is not None else ["segment%d" % i for i in range(len(bufs))]
+    for buf, label in zip(bufs, labels):
+        _issue(buf, label, (0, buf.numel()), overlap=False)
+    scale = _State.scale_fn or ops.scale_inplace
+    ws = _dist().get_world_size()
+    for buf in bufs:
+        scale(buf, 1.0 / ws)
+    _State.issued, _State.pending = [], []
+    return len(bufs)

@@ -23,7 +23,13 @@ The cross-model (back-translation) step is train_cm_step below, and train_step h
 entry points of this module.  unast_amd.train's own train_cm_step / crossmodel_step / train(args) with cm_steps > 0 keep raising CM_REASON for
 model_type='rnn' (flipping that dispatch is a follow-up).
 
-Out of scope (raise NotImplementedError): graph capture, side streams, DDP, B = 1, and autoencoder_step / supervised_step /
+Data parallel.  With torch.distributed initialised every rank runs the sub-steps on its own batch, and RNNFlatAdamW.step sums the
+flat gradient buffers of the segments it is about to step over the ranks and scales them by 1 / world before the clip norm is taken
+(unast_amd.ddp.finish_segments: blocking, on the current stream, one collective per segment).  Which segments step is a function of the
+phase -- text_m and speech_m after generator sub-steps, disc after discriminator sub-steps -- and is checked locally before the first
+collective.  BatchNorm statistics stay per rank; sync_buffers() makes them rank `src`'s before evaluating or saving.
+
+Out of scope (raise NotImplementedError): graph capture, side streams, B = 1, and autoencoder_step / supervised_step /
 crossmodel_step called directly (they would have to return autograd-connected losses).  evaluate() lives in unast_amd.eval_rnn.
 """
 import torch
@@ -34,6 +40,7 @@ from .utils import is_deterministic, next_seed, specaugment
 
 _F32 = torch.float32
 GEN_SEGMENTS = ("text_m", "speech_m")
+PHASE_SEGMENTS = (GEN_SEGMENTS, ("disc",))                 # what one optimizer phase steps, in segment order: the generator phase, the D phase
 CM_REASON = ("the cross-model step is not built for model_type='rnn' behind this entry point: UNAST.cm_text_in / cm_speech_in generate in train mode "
              "-- dropout is on inside greedy decoding and TextPrenet normalises each generated prefix [SOS, c0, ..] with its own batch statistics at "
              "every position -- which the eval generation of this path does not do; train with cm_steps = 0, or call the explicit entry points "
@@ -58,6 +65,25 @@ def drop_cached_operands(model):
     for m in (model.text_m, model.speech_m):
         for slot in PACK_SLOTS:
             m.__dict__.pop(slot, None)
+
+
+def sync_buffers(model, src=0):
+    """Data-parallel runs keep BatchNorm running statistics and num_batches_tracked per rank while training (the reference has no SyncBN; the
+    transformer family's policy).  Before evaluating or saving, this makes every buffer of text_m and speech_m rank `src`'s -- one
+    broadcast per buffer over the launcher's process group -- and drops the cached operand packs, since eval packs fold those statistics.
+    Returns the number of buffers broadcast; 0, and nothing changes, when not distributed."""
+    from . import ddp
+    dist = ddp._dist()
+    if dist is None:
+        return 0
+    n = 0
+    with torch.no_grad():
+        for m in (model.text_m, model.speech_m):
+            for b in m.buffers():
+                dist.broadcast(b, src=src)
+                n += 1
+    drop_cached_operands(model)
+    return n
 
 
 # ---- the optimizer ------------------------------------------------------------------------------------------------------------------------------
@@ -102,15 +128,36 @@ class RNNFlatAdamW(flat_adam.FlatAdam):
                     view.copy_(g)
                 p.grad = view
 
+    def _exchange(self, segs):
+        """Data-parallel step: the gradients of exactly the segments about to step become their mean over the ranks, before the clip
+        norm is taken -- one blocking all-reduce per segment on the current stream, in segment order, then the 1 / world scale.  The disc
+        segment's buffer is the store's gradient range it already holds.
+        Every rank has to issue the same collectives or none of them completes, so which segments step must not depend on a rank's data.  It
+        does not: a generator sub-step (AE, CM or SP) touches both text_m and speech_m, a discriminator sub-step touches disc alone.  That is
+        checked here, locally, before the first collective; a rank that sees anything else raises instead of waiting inside one.
+        Nothing before this point takes part in a collective.  In particular the ranks of a cross-model sub-step generate sequences of
+        different lengths, issue different numbers of launches and read the stop flags back (train_rnn.SYNC_EVERY) at different times: all
+        of that stays local to the rank."""
+        from . import ddp
+        names = tuple(s.name for s in segs)
+        if names not in PHASE_SEGMENTS:
+            raise RuntimeError("data-parallel optimizer step: the segments with gradients are (%s); one optimizer phase steps (%s): generator "
+                               "sub-steps touch text_m and speech_m, discriminator sub-steps touch disc, and every rank must exchange the same "
+                               "segments" % (", ".join(names), ") or (".join(", ".join(p) for p in PHASE_SEGMENTS)))
+        ddp.finish_segments([s.grad for s in segs], names)
+
     @torch.no_grad()
     def step(self, max_norm=0.0, closure=None):
+        from . import ddp
         segs = [s for s in self.segments if self._has_grads(s)]
         self.last_stepped = [s.name for s in segs]
         if not segs:
-            return
+            return                                         # (a phase without sub-steps: a function of args, the same on every rank)
         for s in segs:
             if s.name != "disc":
                 self._adopt_grads(s)
+        if ddp.active():
+            self._exchange(segs)
         self._launch(segs, max_norm)
         if self._store is not None and "disc" in self.last_stepped:
             self._store.refresh_T(["disc"])                # W^T copies and tiled bf16 planes of what was just updated (train.FusedAdamW.step)
@@ -246,9 +293,6 @@ def _check(model, args):
         raise TypeError("model must be UNAST(TextRNN, SpeechRNN[, LSTMDiscriminator]) (train.initialize_model with model_type='rnn')")
     if args.use_discriminator and model.discriminator is None:
         raise ValueError("args.use_discriminator is set but the model has no discriminator")
-    from . import ddp
-    if ddp.active():
-        raise NotImplementedError("model_type='rnn' trains on one device: the data-parallel gradient exchange is not built for this family")
     if not model.training:
         model.train()
 

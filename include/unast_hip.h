@@ -652,6 +652,41 @@ int unast_allreduce(int64_t comm, float* buf, int64_t count, hipStream_t stream)
 int unast_allreduce_marker(float* buf, int64_t count, hipStream_t stream);
 int unast_comm_destroy(int64_t comm);
 
+/* Waveform synthesis (csrc/audio.hip; DESIGN.md section 5q holds the definitions).  Shared conventions: utterance b of a batch has
+ * frames[b] (int32 device array [B], clamped to T_max) frames and hop * (frames[b] - 1) samples; frames at or behind frames[b] and samples
+ * behind that length are neither read nor written.  Spectra are frame-major complex64 [B, T_max, 1 + n_fft/2] (interleaved re, im);
+ * window: the periodic Hann window of win samples, float32 [win]; twiddle: exp(-2 pi i m / n_fft), m < n_fft, complex64 [n_fft] -- both
+ * computed in float64 by the caller.  n_fft is 256, 512, 1024 or 2048, win <= n_fft.  The FFT is a Stockham FFT in LDS, one workgroup per
+ * frame; no sum uses atomics, so results are the same bits on every run and independent of the batch an utterance is in.
+ *
+ * unast_stft: librosa.stft(y, n_fft, hop, win_length=win) (src/utils.py:314; centred, reflect padding done by index arithmetic) of
+ * y [B, ld_y]; needs frames[b] >= n_fft / (2 hop) + 2 (a shorter utterance is skipped; T_max below that is refused).  With mag
+ * (float32 [B, T_max, 1 + n_fft/2], may be NULL) the stored value is mag * e / max(1e-8, |e|): the Griffin-Lim update of src/utils.py:315-316. */
+int unast_stft(const float* y, int64_t ld_y, const int* frames, int B, int T_max, int n_fft, int hop, int win, const float* window,
+               const float* twiddle, const float* mag, float* spec, hipStream_t stream);
+/* The per-frame part of librosa.istft (src/utils.py:328): fr [B, T_max, win] = window * irfft(spec[b,t], n_fft)[(n_fft - win) / 2 + j];
+ * the imaginary parts of the DC and Nyquist bins are ignored; outside the window a frame is zero and is not stored. */
+int unast_istft_frames(const float* spec, const int* frames, int B, int T_max, int n_fft, int win, const float* window, const float* twiddle,
+                       float* fr, hipStream_t stream);
+/* The overlap-add of librosa.istft (src/utils.py:328) as a gather: y[b, m] = (sum of the frames covering sample m, ascending t) / (sum of the
+ * squared window at the same indices), divided only where that sum exceeds FLT_MIN; the n_fft/2 samples at each end are dropped. */
+int unast_overlap_add(const float* fr, const int* frames, int B, int T_max, int n_fft, int hop, int win, const float* window, float* y,
+                      int64_t ld_y, hipStream_t stream);
+/* src/utils.py:292-298: M = (10 ^ (0.05 (clip(mag, 0, 1) max_db - max_db + ref_db))) ^ power for mag [rows, F] with row stride ld_mag
+ * (Vocoder.forward's padded rows are taken as they are); M float32 [rows, F]; X0 (may be NULL) complex64 [rows, F] = (M, 0), the
+ * first iterate of Griffin-Lim (src/utils.py:311). */
+int unast_gl_prepare(const float* mag, int64_t ld_mag, int64_t rows, int F, double max_db, double ref_db, double power, float* M, float* X0,
+                     hipStream_t stream);
+/* scipy.signal.lfilter([1], [1, -coef]) (src/utils.py:301): y[b,k] = x[b,k] + coef y[b,k-1] over the first lens[b] samples of each row, as a
+ * blocked scan (16 samples per thread, 4096 per tile; chunk ends combined with coef^16).  y may be x. */
+int unast_deemphasis(const float* x, int64_t ld_x, float* y, int64_t ld_y, const int* lens, int B, float coef, hipStream_t stream);
+/* The interval librosa.effects.trim keeps (src/utils.py:304): out int32 [B, 2] = {start, end} in samples of y [B, ld_y] with lens[b] <= n_max
+ * samples.  Centred frames of frame_length at hop_length over the signal padded by frame_length / 2 (pad_mode 0: reflect, librosa 0.8;
+ * 1: zeros, later versions); a frame is kept when 10 log10(max(1e-10, mean square)) is within top_db of the loudest frame's.
+ * ws: B * (1 + n_max / hop_length) floats (receives the frame mean squares). */
+int unast_trim_bounds(const float* y, int64_t ld_y, const int* lens, int B, int n_max, float top_db, int frame_length, int hop_length, int pad_mode,
+                      float* ws, int64_t ws_floats, int* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

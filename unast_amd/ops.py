@@ -1567,6 +1567,139 @@ def edit_distance(ref, ref_len, hyp, hyp_len, out=None, ws=None, chunk=0):
     return out
 
 
+# ---- waveform synthesis (csrc/audio.hip) -------------------------------------------------------------------
+STFT_SIZES = (256, 512, 1024, 2048)                 # n_fft the LDS FFT is built for
+DEEMPH_CHUNK, DEEMPH_TILE = 16, 4096                # samples per thread and per workgroup tile of the de-preemphasis scan (the kernel's own constants)
+_C64 = torch.complex64
+
+
+def _audio_t(who, t, name, dtype, shape=None):
+    kind = {_F32: "float32", _C64: "complex64", torch.int32: "int32"}[dtype]
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype):
+        raise TypeError("%s: %s must be a %s CUDA tensor (got %s)" % (who, name, kind, (t.dtype, str(t.device)) if torch.is_tensor(t) else type(t)))
+    if not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError("%s: %s must be contiguous%s (got %s)" % (who, name, "" if shape is None else " of shape %s" % (tuple(shape),), tuple(t.shape)))
+
+
+def _stft_geometry(who, n_fft, hop, win):
+    if n_fft not in STFT_SIZES:
+        raise ValueError("%s: n_fft must be one of %s (got %r)" % (who, STFT_SIZES, n_fft))
+    if not 1 <= win <= n_fft:
+        raise ValueError("%s: win must be in 1..n_fft (win > n_fft has no centred padding; got win=%r, n_fft=%d)" % (who, win, n_fft))
+    if hop < 1:
+        raise ValueError("%s: hop must be positive (got %r)" % (who, hop))
+
+
+def _rows_2d(who, t, name, min_cols):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == _F32):
+        raise TypeError("%s: %s must be a float32 CUDA tensor (got %s)" % (who, name, (t.dtype, str(t.device)) if torch.is_tensor(t) else type(t)))
+    if t.dim() != 2 or t.shape[1] < min_cols or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("%s: %s must be [B, >= %d] with unit column stride (got %s)" % (who, name, min_cols, tuple(t.shape)))
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def stft(y, frames, T_max, n_fft, hop, win, window, twiddle, spec, mag=None):
+    """spec complex64 [B,T_max,1+n_fft/2] = the centred, reflect-padded STFT of y [B, >= hop (T_max-1)]; frames int32 [B].  With mag
+    float32 [B,T_max,1+n_fft/2] the Griffin-Lim update mag * e / max(1e-8, |e|) is stored instead of e."""
+    _stft_geometry("stft", n_fft, hop, win)
+    F_ = n_fft // 2 + 1
+    _audio_t("stft", frames, "frames", torch.int32)
+    B = frames.numel()
+    ld = _rows_2d("stft", y, "y", hop * (T_max - 1))
+    _audio_t("stft", spec, "spec", _C64, (B, T_max, F_))
+    _audio_t("stft", window, "window", _F32, (win,))
+    _audio_t("stft", twiddle, "twiddle", _C64, (n_fft,))
+    if mag is not None:
+        _audio_t("stft", mag, "mag", _F32, (B, T_max, F_))
+    if y.shape[0] != B:
+        raise ValueError("stft: y has %d rows, frames %d" % (y.shape[0], B))
+    check(lib().unast_stft(_p(y), ld, _p(frames), B, T_max, n_fft, hop, win, _p(window), _p(twiddle), _p(mag), _p(spec), _stream()), "unast_stft")
+    return spec
+
+
+def istft_frames(spec, frames, n_fft, win, window, twiddle, fr):
+    """fr float32 [B,T_max,win] = window * irfft(spec[b,t])[(n_fft-win)/2 : (n_fft-win)/2 + win] for t < frames[b]."""
+    _stft_geometry("istft_frames", n_fft, 1, win)
+    _audio_t("istft_frames", frames, "frames", torch.int32)
+    _audio_t("istft_frames", spec, "spec", _C64)
+    if spec.dim() != 3 or spec.shape[0] != frames.numel() or spec.shape[2] != n_fft // 2 + 1:
+        raise ValueError("istft_frames: spec must be [B, T, %d] with B = len(frames) (got %s)" % (n_fft // 2 + 1, tuple(spec.shape)))
+    B, T_max = spec.shape[0], spec.shape[1]
+    _audio_t("istft_frames", fr, "fr", _F32, (B, T_max, win))
+    _audio_t("istft_frames", window, "window", _F32, (win,))
+    _audio_t("istft_frames", twiddle, "twiddle", _C64, (n_fft,))
+    check(lib().unast_istft_frames(_p(spec), _p(frames), B, T_max, n_fft, win, _p(window), _p(twiddle), _p(fr), _stream()), "unast_istft_frames")
+    return fr
+
+
+def overlap_add(fr, frames, n_fft, hop, window, y):
+    """y [B, >= hop (T_max-1)] = the frames fr [B,T_max,win] overlap-added and divided by the window's sum of squares (a gather, no atomics)."""
+    _audio_t("overlap_add", fr, "fr", _F32)
+    if fr.dim() != 3:
+        raise ValueError("overlap_add: fr must be [B, T, win] (got %s)" % (tuple(fr.shape),))
+    B, T_max, win = fr.shape
+    _stft_geometry("overlap_add", n_fft, hop, win)
+    _audio_t("overlap_add", frames, "frames", torch.int32, (B,))
+    _audio_t("overlap_add", window, "window", _F32, (win,))
+    ld = _rows_2d("overlap_add", y, "y", hop * (T_max - 1))
+    if y.shape[0] != B:
+        raise ValueError("overlap_add: y has %d rows, fr %d" % (y.shape[0], B))
+    check(lib().unast_overlap_add(_p(fr), _p(frames), B, T_max, n_fft, hop, win, _p(window), _p(y), ld, _stream()), "unast_overlap_add")
+    return y
+
+
+def gl_prepare(mag, max_db, ref_db, power, M, X0=None):
+    """M = (10 ** (0.05 * (clip(mag, 0, 1) * max_db - max_db + ref_db))) ** power for mag [..., F] with unit column stride and one row stride
+    (a view of a padded buffer qualifies); X0 (complex64, optional) = M + 0j."""
+    if not (torch.is_tensor(mag) and mag.is_cuda and mag.dtype == _F32):
+        raise TypeError("gl_prepare: mag must be a float32 CUDA tensor (got %s)" % ((mag.dtype, str(mag.device)) if torch.is_tensor(mag) else type(mag),))
+    if mag.dim() < 2 or mag.numel() == 0:
+        raise ValueError("gl_prepare: mag must be [..., rows, F], not empty")
+    F_ = mag.shape[-1]
+    rows = mag.numel() // F_
+    ld = mag.stride(-2) if rows > 1 else F_
+    one_row_stride = all(mag.shape[i] == 1 or mag.stride(i) == mag.stride(i + 1) * mag.shape[i + 1] for i in range(mag.dim() - 2))
+    if (F_ > 1 and mag.stride(-1) != 1) or ld < F_ or not one_row_stride:
+        raise ValueError("gl_prepare: mag needs unit column stride and one row stride (got shape %s, strides %s)" % (tuple(mag.shape), mag.stride()))
+    _audio_t("gl_prepare", M, "M", _F32, mag.shape)
+    if X0 is not None:
+        _audio_t("gl_prepare", X0, "X0", _C64, mag.shape)
+    check(lib().unast_gl_prepare(_p(mag), ld, rows, F_, max_db, ref_db, power, _p(M), _p(X0), _stream()), "unast_gl_prepare")
+    return M
+
+
+def deemphasis(x, lens, coef, y):
+    """y[b,k] = x[b,k] + coef * y[b,k-1] over the first lens[b] samples of each row of x [B,n]; y may be x."""
+    _audio_t("deemphasis", lens, "lens", torch.int32)
+    ldx = _rows_2d("deemphasis", x, "x", 0)
+    ldy = _rows_2d("deemphasis", y, "y", 0)
+    if x.shape != y.shape or x.shape[0] != lens.numel() or x.shape[1] < 1:
+        raise ValueError("deemphasis: x and y [B, n >= 1] of one shape, lens [B]")
+    if not -1.0 < coef < 1.0:
+        raise ValueError("deemphasis: |coef| must be below 1 (got %r)" % coef)
+    check(lib().unast_deemphasis(_p(x), ldx, _p(y), ldy, _p(lens), x.shape[0], coef, _stream()), "unast_deemphasis")
+    return y
+
+
+def trim_bounds(y, lens, top_db, frame_length, hop_length, pad_mode, out=None):
+    """out int32 [B,2] = (start, end) of librosa.effects.trim for each row of y [B,n] with lens[b] samples; pad_mode 'reflect' or 'constant'."""
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError("trim_bounds: pad_mode is 'reflect' (librosa 0.8) or 'constant' (later versions), got %r" % (pad_mode,))
+    _audio_t("trim_bounds", lens, "lens", torch.int32)
+    ld = _rows_2d("trim_bounds", y, "y", 1)
+    B, n_max = y.shape
+    if lens.numel() != B or frame_length < 2 or hop_length < 1 or top_db <= 0:
+        raise ValueError("trim_bounds: lens [B], frame_length >= 2, hop_length >= 1, top_db > 0")
+    if out is None:
+        out = torch.empty(B, 2, dtype=torch.int32, device=y.device)
+    else:
+        _audio_t("trim_bounds", out, "out", torch.int32, (B, 2))
+    ws = torch.empty(B * (1 + n_max // hop_length), dtype=_F32, device=y.device)
+    check(lib().unast_trim_bounds(_p(y), ld, _p(lens), B, n_max, top_db, frame_length, hop_length, 0 if pad_mode == "reflect" else 1, _p(ws), ws.numel(),
+                                  _p(out), _stream()), "unast_trim_bounds")
+    return out
+
+
 # ---- optimizer ---------------------------------------------------------------------------------------------
 _MSE_WS = {}
 

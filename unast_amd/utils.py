@@ -168,3 +168,9 @@ def compare_outputs(ground_truth, hypothesis, gt_len, hyp_len):
     """src/utils.py:36-38; prints ids (the symbol table belongs to the reference's text front end, outside this path)."""
     print("Model prediction of length %d " % int(hyp_len), _to_lists(hypothesis)[:int(hyp_len)])
     print("Ground Truth of length %d " % int(gt_len), _to_lists(ground_truth)[:int(gt_len)])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Waveform synthesis (src/utils.py:281-328) under the reference's names; spectra are frame-major here (unast_amd/audio.py)
+# ---------------------------------------------------------------------------------------------------------------
+from .audio import griffin_lim, invert_spectrogram, spectrogram2wav  # noqa: E402,F401

@@ -8,8 +8,9 @@ edits): conv weights tap-major [Cout,k,Cin] with the eval BatchNorm folded in, e
 [512,256] matrix, each GRU layer's weight_ih of both directions as one [768,256] matrix.
 
 Supported: Vocoder(num_mels, 256, num_fft) with num_mels a multiple of 4 (the reference builds Vocoder(80, 256, 2048)); eval mode under
-torch.no_grad() only.  Training has its own entry point, unast_amd.train_vocoder.vocoder_step (this forward keeps refusing train mode);
-Griffin-Lim / spectrogram2wav are not part of this package.
+torch.no_grad() only.  Training has its own entry point, unast_amd.train_vocoder.vocoder_step (this forward keeps refusing train mode).
+The magnitudes become waveforms in unast_amd.audio (spectrogram2wav_batch, mel2wav: Griffin-Lim on csrc/audio.hip), which reads this
+forward's output as it is, padded rows included.
 """
 import torch
 import torch.nn as nn

@@ -687,6 +687,23 @@ int unast_deemphasis(const float* x, int64_t ld_x, float* y, int64_t ld_y, const
 int unast_trim_bounds(const float* y, int64_t ld_y, const int* lens, int B, int n_max, float top_db, int frame_length, int hop_length, int pad_mode,
                       float* ws, int64_t ws_floats, int* out, hipStream_t stream);
 
+/* Feature extraction (csrc/audio.hip; DESIGN.md section 5r holds the definitions): get_spectrograms (src/utils.py:235-278) from the preemphasis
+ * on.  Utterance b is the samples[b] samples of row b of y [B, ld_y] from start[b] on (int32 device arrays [B]; start may be NULL: zeros) and
+ * has 1 + samples[b] / hop frames; one that is not longer than n_fft / 2, or reaches outside [0, n_max), is skipped.  Per frame: the windowed
+ * frame of e[k] = y[k] - coef y[k-1], e[0] = y[0] (:251; multiply and subtract rounded separately, as numpy does), its transform (:254; reflect
+ * padding about samples 0 and samples[b] - 1), |S| (:260), mel = basis |S| (:263-264; basis float32 [n_mels, 1 + n_fft/2] dense, read only inside
+ * ranges int32 [n_mels, 2] = each filter's [lo, hi), summed by one thread in ascending bin order), and for both
+ * clip((20 log10(max(1e-5, x)) - ref_db + max_db) / max_db, 1e-8, 1) (:267-272).  mel float32 [B, T_max, n_mels], mag float32
+ * [B, T_max, 1 + n_fft/2] (:275-276); spec (may be NULL) complex64 [B, T_max, 1 + n_fft/2] receives S itself, the same bits unast_stft gives for
+ * the emphasised signal.  Frames at or behind an utterance's count are not written.  T_max below 1 + (n_fft / 2 + 1) / hop is refused. */
+int unast_features(const float* y, int64_t ld_y, int n_max, const int* start, const int* samples, int B, int T_max, int n_fft, int hop, int win,
+                   float coef, const float* window, const float* twiddle, const float* basis, const int* ranges, int n_mels, float ref_db,
+                   float max_db, float* mel, float* mag, float* spec, hipStream_t stream);
+/* src/utils.py:251, np.append(y[0], y[1:] - coef * y[:-1]) in float32, bit for bit: y[b, start[b] + k] = x[b, start[b] + k] - coef x[b, start[b] + k - 1]
+ * for 0 < k < lens[b], the raw sample at k = 0; rows [B, n_max] with strides ld_x, ld_y; start may be NULL.  Not in place. */
+int unast_preemphasis(const float* x, int64_t ld_x, float* y, int64_t ld_y, int n_max, const int* start, const int* lens, int B, float coef,
+                      hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ Spectra are frame-major [frames, 1 + n_fft/2], the layout Vocoder.forward produc
 Griffin-Lim iteration is three launches (inverse transforms, overlap-add gather, forward transforms with the phase update in their epilogue);
 the utterances of a batch run side by side and each one's result is bit-identical to running it alone.
 
-`librosa.griffinlim` as gl_vocoder.py calls it (random initial phase, momentum) is not this path and is not built."""
+`librosa.griffinlim` as gl_vocoder.py calls it (random initial phase, momentum) is not this path and is not built.
+
+The other direction, feature extraction: the reference's get_spectrograms (src/utils.py:235-278 -- load, trim, preemphasis, stft, |S|, mel
+basis, dB, normalise, clip) and prepare_data.py's loop over a folder of wavs, a batch of utterances per launch.  The mel
+basis is librosa.filters.mel at its defaults written out; resampling is not built, so a file at another rate than sr is refused."""
 import os
 import wave
 from dataclasses import dataclass
@@ -24,7 +28,7 @@ _F32 = torch.float32
 @dataclass(frozen=True)
 class AudioParams:
     """The reference's audio settings (src/audio_parameters.py: n_fft :4, sr :5, preemphasis :8, hop_length = int(sr * 0.0125) :9-11,
-    win_length = int(sr * 0.05) :10-12, power :14, max_db :17, ref_db :18, n_iter :19)."""
+    win_length = int(sr * 0.05) :10-12, power :14, max_db :17, ref_db :18, n_iter :19, n_mels :13)."""
     n_fft: int = 2048
     hop: int = 275
     win: int = 1102
@@ -34,6 +38,7 @@ class AudioParams:
     ref_db: float = 20.0
     n_iter: int = 60
     sr: int = 22050
+    n_mels: int = 80
 
     @property
     def bins(self):
@@ -313,4 +318,172 @@ def vocode(names, mags_dir, out_dir, params=AudioParams(), pad_mode="reflect", d
         wavs = spectrogram2wav_batch(torch.from_numpy(padded).to(device), lens, params, True, pad_mode)
         for n, w in zip(part, wavs):
             out.append(write_wav(os.path.join(out_dir, "%s.wav" % n), w, params.sr))
+    return out
+
+
+# ---- feature extraction (src/utils.py:235-278, src/prepare_data.py) ------------------------------------------------------------------
+_MEL = {}
+
+
+def _mel_basis_host(p):
+    """librosa.filters.mel(sr, n_fft, n_mels) at its defaults (fmin 0, fmax sr / 2, Slaney scale, Slaney norm), float64 rounded once."""
+    key = (p.sr, p.n_fft, p.n_mels)
+    if key not in _MEL:
+        step, knee, logstep = 200.0 / 3.0, 1000.0, np.log(6.4) / 27.0
+
+        def to_mel(f):
+            return f / step if f < knee else knee / step + np.log(f / knee) / logstep
+        pts = np.linspace(to_mel(0.0), to_mel(p.sr / 2.0), p.n_mels + 2)
+        m = np.where(pts < knee / step, pts * step, knee * np.exp((pts - knee / step) * logstep))          # the filters' edges in Hz
+        f = np.arange(p.bins, dtype=np.float64) * p.sr / p.n_fft
+        W = np.zeros((p.n_mels, p.bins))
+        for i in range(p.n_mels):
+            tri = np.minimum((f - m[i]) / (m[i + 1] - m[i]), (m[i + 2] - f) / (m[i + 2] - m[i + 1]))
+            W[i] = np.maximum(0.0, tri) * 2.0 / (m[i + 2] - m[i])
+        W = W.astype(np.float32)
+        ranges = np.zeros((p.n_mels, 2), dtype=np.int32)
+        for i in range(p.n_mels):
+            nz = np.flatnonzero(W[i])
+            if nz.size:                                      # contiguous: a triangle; a filter narrower than a bin's spacing may hold none
+                ranges[i] = (nz[0], nz[-1] + 1)
+        W.setflags(write=False)
+        ranges.setflags(write=False)
+        _MEL[key] = (W, ranges)
+    return _MEL[key]
+
+
+def mel_basis(params=AudioParams(), device=None):
+    """(W float32 [n_mels, bins], ranges int32 [n_mels, 2]): the mel filterbank and each filter's [lo, hi) of nonzero bins ((0, 0) for an empty
+    filter), read-only numpy arrays; with a device, the same two as tensors there (cached per device, like the window and twiddle tables)."""
+    p = params
+    if p.n_mels < 1:
+        raise ValueError("mel_basis: n_mels must be positive (got %r)" % (p.n_mels,))
+    if p.n_fft < 2 or p.n_fft % 2 or p.sr <= 0:
+        raise ValueError("mel_basis: n_fft must be even and sr positive (got n_fft=%r, sr=%r)" % (p.n_fft, p.sr))
+    W, ranges = _mel_basis_host(p)
+    if device is None:
+        return W, ranges
+    key = (p.sr, p.n_fft, p.n_mels, str(device))
+    if key not in _MEL:
+        _MEL[key] = (torch.from_numpy(W.copy()).to(device), torch.from_numpy(ranges.copy()).to(device))
+    return _MEL[key]
+
+
+def preemphasis(y, lens=None, coef=AudioParams.preemphasis):
+    """np.append(y[0], y[1:] - coef * y[:-1]) (src/utils.py:251) in float32, numpy's bits, for y [n] or [B, n]; lens: samples per row (default:
+    all); samples behind a row's length are left unwritten (zero here)."""
+    _need_cuda("preemphasis", y, "y")
+    single = y.dim() == 1
+    y2 = (y.unsqueeze(0) if single else y).contiguous()
+    lens = [y2.shape[1]] * y2.shape[0] if lens is None else [int(n) for n in lens]
+    if len(lens) != y2.shape[0] or any(n < 0 or n > y2.shape[1] for n in lens):
+        raise ValueError("preemphasis: one length per row is needed, each within 0..%d" % y2.shape[1])
+    out = ops.preemphasis(y2, _i32(lens, y2.device), float(coef), torch.zeros_like(y2))
+    return out[0] if single else out
+
+
+def get_spectrograms_batch(y, lens, params=AudioParams(), trim=True, pad_mode="reflect", starts=None, return_spec=False):
+    """src/utils.py:248-276 for a batch: y float32 [B, n_max] on the device, lens samples per row -> (mel [B, T_max, n_mels], mag [B, T_max, bins],
+    frames): normalised, frame-major, frames[b] = 1 + n_b // hop with n_b the samples left after trimming; rows at or behind frames[b] are zero.
+    trim: librosa.effects.trim at its defaults first (one read-back of the bounds); starts (without trim): utterance b begins at starts[b] of
+    its row.  return_spec: the complex64 spectrum of the emphasised signal as a fourth result.  One launch for the whole batch; an utterance's
+    result is bit-identical to running it alone."""
+    who = "get_spectrograms_batch"
+    p = params
+    _check_params(who, p)
+    if p.n_mels < 1:
+        raise ValueError("%s: n_mels must be positive (got %r)" % (who, p.n_mels))
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError("%s: pad_mode is 'reflect' (librosa 0.8) or 'constant' (later versions), got %r" % (who, pad_mode))
+    if not torch.is_tensor(y) or y.dim() != 2:
+        raise ValueError("%s: y must be [B, n_max]" % who)
+    B, n_max = y.shape
+    lens = [int(n) for n in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+    if len(lens) != B or B < 1:
+        raise ValueError("%s: %d rows, %d lengths" % (who, B, len(lens)))
+    if trim and starts is not None:
+        raise ValueError("%s: starts are given without trim (trim finds them)" % who)
+    starts = [0] * B if starts is None else [int(v) for v in starts]
+    if len(starts) != B or any(s < 0 or n < 1 or s + n > n_max for s, n in zip(starts, lens)):
+        raise ValueError("%s: an utterance lies outside its row of %d samples (starts %s, lengths %s)" % (who, n_max, starts, lens))
+
+    def long_enough(counts, when):
+        for b, n in enumerate(counts):
+            if n <= p.n_fft // 2:
+                raise ValueError("%s: utterance %d has %d samples%s, too short: more than n_fft / 2 = %d are needed for the signal to be longer than "
+                                 "the reflect padding" % (who, b, n, when, p.n_fft // 2))
+    long_enough(lens, "")
+    _need_cuda(who, y, "y")
+    if y.dtype != _F32:
+        raise TypeError("%s: y must be float32 (got %s)" % (who, y.dtype))
+    dev = y.device
+    with torch.no_grad():
+        y = y if y.stride(1) == 1 else y.contiguous()
+        if trim:
+            bounds = ops.trim_bounds(y, _i32(lens, dev), 60.0, 2048, 512, pad_mode).tolist()
+            starts, samples = [s for s, _ in bounds], [e - s for s, e in bounds]
+            long_enough(samples, " after trimming")
+        else:
+            samples = lens
+        frames = [1 + n // p.hop for n in samples]
+        T_max = max(frames)
+        window, tw = _tables(p, dev)
+        W, ranges = mel_basis(p, dev)
+        mel = torch.zeros(B, T_max, p.n_mels, dtype=_F32, device=dev)
+        mag = torch.zeros(B, T_max, p.bins, dtype=_F32, device=dev)
+        spec = torch.zeros(B, T_max, p.bins, dtype=torch.complex64, device=dev) if return_spec else None
+        ops.features(y, _i32(starts, dev), _i32(samples, dev), T_max, p.n_fft, p.hop, p.win, float(p.preemphasis), window, tw, W, ranges,
+                     float(p.ref_db), float(p.max_db), mel, mag, spec)
+    return (mel, mag, frames, spec) if return_spec else (mel, mag, frames)
+
+
+def load_wav(path, sr=AudioParams.sr):
+    """librosa.load(path, sr=sr) (src/utils.py:245) for what the reference feeds it, through the standard library's wave: 16-bit PCM read as
+    int / 32768, channels averaged, float32 [n].  Resampling is not built: a file at another rate is refused, as is another sample width."""
+    with wave.open(path, "rb") as f:
+        ch, width, rate, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        raw = f.readframes(n)
+    if width != 2:
+        raise ValueError("load_wav: %s holds %d-bit samples; only 16-bit PCM is read" % (path, 8 * width))
+    if rate != int(sr):
+        raise ValueError("load_wav: %s is sampled at %d Hz, not %d: resampling is not built, convert the file first" % (path, rate, int(sr)))
+    x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768.0)
+    return x.reshape(-1, ch).mean(axis=1, dtype=np.float32) if ch > 1 else x
+
+
+def _features_of(wavs, p, pad_mode, device):
+    """[(mel [T, n_mels], mag [T, bins])] float32 numpy for a list of 1-D float32 numpy waveforms: one batch."""
+    lens = [len(w) for w in wavs]
+    padded = np.zeros((len(wavs), max(lens)), dtype=np.float32)
+    for b, w in enumerate(wavs):
+        padded[b, :lens[b]] = w
+    mel, mag, frames = get_spectrograms_batch(torch.from_numpy(padded).to(device), lens, p, True, pad_mode)
+    mel, mag = mel.cpu().numpy(), mag.cpu().numpy()
+    return [(mel[b, :T].copy(), mag[b, :T].copy()) for b, T in enumerate(frames)]
+
+
+def get_spectrograms(fpath, params=AudioParams(), pad_mode="reflect", device="cuda"):
+    """The reference's signature (src/utils.py:235-278): a wav file -> (mel [T, n_mels], mag [T, 1 + n_fft/2]) float32 numpy, normalised."""
+    y = load_wav(fpath, params.sr)
+    if not torch.cuda.is_available():
+        raise RuntimeError("get_spectrograms: needs a CUDA (ROCm) device: the transforms are HIP kernels and have no CPU path")
+    return _features_of([y], params, pad_mode, device)[0]
+
+
+def prepare_data(names, wav_dir, out_dir=None, params=AudioParams(), pad_mode="reflect", device="cuda", batch=32):
+    """src/prepare_data.py's loop, `batch` files per launch: reads <wav_dir>/<name>.wav and writes <name>.pt.npy (mel, what unast_amd.data and
+    train_vocoder.py read) and <name>.mag.npy (what train_vocoder.py and vocode read) next to the wavs, or under out_dir.  Returns the
+    (mel path, mag path) pairs written."""
+    out_dir = wav_dir if out_dir is None else out_dir
+    os.makedirs(out_dir, exist_ok=True)
+    names = list(names)
+    out = []
+    for i in range(0, len(names), batch):
+        part = names[i:i + batch]
+        feats = _features_of([load_wav(os.path.join(wav_dir, "%s.wav" % n), params.sr) for n in part], params, pad_mode, device)
+        for n, (mel, mag) in zip(part, feats):
+            paths = (os.path.join(out_dir, "%s.pt.npy" % n), os.path.join(out_dir, "%s.mag.npy" % n))
+            np.save(paths[0], mel)
+            np.save(paths[1], mag)
+            out.append(paths)
     return out

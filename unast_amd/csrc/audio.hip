@@ -2,6 +2,8 @@
 // Fourier transform and its inverse at librosa's settings (centred frames, reflect padding, a periodic Hann window of win samples centred in
 // n_fft, overlap-add divided by the window's sum of squares), the Griffin-Lim phase update, the de-normalisation, the de-preemphasis
 // recurrence and the bounds of librosa.effects.trim.  DESIGN.md section 5q states the definitions these kernels are held to.
+// Feature extraction, the other direction (src/utils.py:235-278, get_spectrograms): the preemphasis, the transform over an arbitrary sample
+// count and, in its epilogue, |S|, the mel projection, dB, normalise and clip.
 //
 // The transform is a Stockham autosort FFT in LDS, written here: one workgroup of 256 threads per frame, the frame as n_fft complex points
 // (2048 x 8 bytes = 16 KB per buffer, two buffers), radix-4 passes and one closing radix-2 pass where log2(n_fft) is odd
@@ -340,6 +342,86 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_bounds_kernel(const float* 
     }
 }
 
+// e[0] = y[0], e[k] = y[k] - c y[k-1] (src/utils.py:251) as numpy forms it on a float32 array: one rounded multiply, one rounded subtract,
+// never an FMA (hipcc contracts a * b - c by default, through __fmul_rn / __fsub_rn as well, so contraction is switched off for this
+// function's arithmetic).  yb points at the utterance's first sample, k >= 0.
+__device__ __forceinline__ float emphasised(const float* __restrict__ yb, int k, float c) {
+#pragma clang fp contract(off)
+    const float v = yb[k];
+    if (k == 0) return v;
+    const float prod = c * yb[k - 1];
+    return v - prod;
+}
+
+// clip((20 log10(max(1e-5, x)) - ref_db + max_db) / max_db, 1e-8, 1) (src/utils.py:267-272)
+__device__ __forceinline__ float normalised_db(float x, float ref_db, float max_db) {
+    const float v = (20.f * log10f(fmaxf(1e-5f, x)) - ref_db + max_db) / max_db;
+    return fminf(fmaxf(v, 1e-8f), 1.f);
+}
+
+// get_spectrograms (src/utils.py:251-276) for frame t of utterance b, the samples[b] samples of row b from start[b] on: the windowed frame of
+// the emphasised signal (reflect padding by index arithmetic about samples 0 and n - 1; index 0 keeps its raw value), the transform, and in
+// its epilogue |S| into the LDS buffer the transform has finished with, the normalised magnitude row, and -- after a barrier -- the mel
+// values, one thread per filter summing W[i,k] |S[k]| over the filter's [lo, hi) in ascending k, normalised the same way.  An utterance that
+// is not longer than the padding, or does not lie inside its row, is skipped; so are frames at or behind 1 + n / hop.
+__global__ __launch_bounds__(FFT_THREADS) void features_kernel(const float* __restrict__ y, long long ld_y, int n_max, const int* __restrict__ start,
+                                                               const int* __restrict__ samples, int T_max, int N, int hop, int win, float coef,
+                                                               const float* __restrict__ window, const float2* __restrict__ tw,
+                                                               const float* __restrict__ basis, const int* __restrict__ ranges, int n_mels, float ref_db,
+                                                               float max_db, float* __restrict__ mel, float* __restrict__ magn, float2* __restrict__ spec) {
+    __shared__ FftLds s;
+    const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+    const int n = samples[b], st = start ? start[b] : 0, half = N >> 1;
+    if (n <= half || st < 0 || n > n_max - st || t >= 1 + n / hop) return;      // uniform over the workgroup
+    const int lpad = (N - win) >> 1;
+    const float* yb = y + (size_t)b * ld_y + st;
+    for (int m = tid; m < N; m += FFT_THREADS) {
+        const int j = m - lpad;
+        float v = 0.f;
+        if (j >= 0 && j < win) {
+            int p = t * hop + m - half;
+            if (p < 0) p = -p;
+            if (p >= n) p = 2 * (n - 1) - p;
+            p = max(0, min(p, n - 1));
+            v = window[j] * emphasised(yb, p, coef);
+        }
+        const int pi = padi(m);
+        s.re[0][pi] = v;
+        s.im[0][pi] = 0.f;
+    }
+    __syncthreads();
+    const int cur = fft_lds<false>(s, tw, N);
+    const int F = half + 1;
+    const size_t fi = (size_t)b * T_max + t;
+    float* absS = s.re[cur ^ 1];                              // the last pass read it; a barrier has passed since
+    for (int k = tid; k < F; k += FFT_THREADS) {
+        const int pi = padi(k);
+        const float re = s.re[cur][pi], im = s.im[cur][pi];
+        const float a = sqrtf(__builtin_fmaf(re, re, im * im));
+        absS[pi] = a;
+        magn[fi * F + k] = normalised_db(a, ref_db, max_db);
+        if (spec) spec[fi * F + k] = make_float2(re, im);
+    }
+    __syncthreads();
+    for (int i = tid; i < n_mels; i += FFT_THREADS) {
+        const int lo = max(0, ranges[2 * i]), hi = min(F, ranges[2 * i + 1]);
+        const float* w = basis + (size_t)i * F;
+        float acc = 0.f;
+        for (int k = lo; k < hi; ++k) acc = __builtin_fmaf(w[k], absS[padi(k)], acc);
+        mel[fi * n_mels + i] = normalised_db(acc, ref_db, max_db);
+    }
+}
+
+// out[b, start[b] + k] = the emphasised sample k of the utterance x[b, start[b] : start[b] + lens[b]]; nothing else is read or written.
+__global__ __launch_bounds__(256) void preemphasis_kernel(const float* __restrict__ x, long long ld_x, float* __restrict__ out, long long ld_out, int n_max,
+                                                          const int* __restrict__ start, const int* __restrict__ lens, float coef) {
+    const int b = blockIdx.y;
+    const int n = lens[b], st = start ? start[b] : 0;
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n < 1 || st < 0 || n > n_max - st || k >= n) return;
+    out[(size_t)b * ld_out + st + k] = emphasised(x + (size_t)b * ld_x + st, (int)k, coef);
+}
+
 int check_stft_params(const char* who, int B, int T_max, int n_fft, int hop, int win) {
     UNAST_REQUIRE(B >= 1 && B <= 65535 && T_max >= 1, "%s: need 1 <= B <= 65535 and T_max >= 1 (B=%d T_max=%d)", who, B, T_max);
     UNAST_REQUIRE(n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048, "%s: n_fft must be 256, 512, 1024 or 2048 (got %d)", who, n_fft);
@@ -419,4 +501,32 @@ extern "C" int unast_trim_bounds(const float* y, int64_t ld_y, const int* lens, 
                        pad_mode == 0 ? 1 : 0, ws);
     hipLaunchKernelGGL(trim_bounds_kernel, dim3(B), dim3(TRIM_THREADS), 0, stream, (const float*)ws, lens, nf_max, hop_length, top_db, out);
     return unast_check_launch("unast_trim_bounds");
+}
+
+extern "C" int unast_features(const float* y, int64_t ld_y, int n_max, const int* start, const int* samples, int B, int T_max, int n_fft, int hop, int win,
+                              float coef, const float* window, const float* twiddle, const float* basis, const int* ranges, int n_mels, float ref_db,
+                              float max_db, float* mel, float* mag, float* spec, hipStream_t stream) {
+    if (int rc = check_stft_params("unast_features", B, T_max, n_fft, hop, win)) return rc;
+    UNAST_REQUIRE(y && samples && window && twiddle && basis && ranges && mel && mag, "unast_features: null pointer");
+    UNAST_REQUIRE(hop <= win, "unast_features: hop must not exceed win: a larger hop leaves samples no frame covers (hop=%d win=%d)", hop, win);
+    UNAST_REQUIRE(n_mels >= 1 && n_mels <= 4096, "unast_features: need 1 <= n_mels <= 4096 (got %d)", n_mels);
+    UNAST_REQUIRE(max_db > 0.f, "unast_features: max_db must be positive (got %g)", (double)max_db);
+    const int min_frames = 1 + (n_fft / 2 + 1) / hop;
+    UNAST_REQUIRE(T_max >= min_frames, "unast_features: T_max = %d holds no utterance: the shortest one, n_fft / 2 + 1 samples (the signal must be longer than the reflect "
+                  "padding), has %d frames", T_max, min_frames);
+    UNAST_REQUIRE(n_max > n_fft / 2 && n_max < (1 << 30) && ld_y >= n_max, "unast_features: need n_fft / 2 < n_max < 2^30 and a row stride of at least n_max (n_max=%d ld_y=%lld)",
+                  n_max, (long long)ld_y);
+    UNAST_REQUIRE((((uintptr_t)twiddle) & 7) == 0 && (((uintptr_t)spec) & 7) == 0, "unast_features: twiddle and spec hold complex values and need 8-byte alignment");
+    hipLaunchKernelGGL(features_kernel, dim3(T_max, B), dim3(FFT_THREADS), 0, stream, y, (long long)ld_y, n_max, start, samples, T_max, n_fft, hop, win, coef, window,
+                       (const float2*)twiddle, basis, ranges, n_mels, ref_db, max_db, mel, mag, (float2*)spec);
+    return unast_check_launch("unast_features");
+}
+
+extern "C" int unast_preemphasis(const float* x, int64_t ld_x, float* y, int64_t ld_y, int n_max, const int* start, const int* lens, int B, float coef,
+                                 hipStream_t stream) {
+    UNAST_REQUIRE(x && y && lens && B >= 1 && B <= 65535, "unast_preemphasis: need x, y, lens and 1 <= B <= 65535 (B=%d)", B);
+    UNAST_REQUIRE(x != y, "unast_preemphasis: not in place: sample k reads sample k - 1 of the input");
+    UNAST_REQUIRE(n_max >= 1 && n_max < (1 << 30) && ld_x >= n_max && ld_y >= n_max, "unast_preemphasis: need 1 <= n_max < 2^30 and row strides of at least n_max (n_max=%d)", n_max);
+    hipLaunchKernelGGL(preemphasis_kernel, dim3((unsigned)((n_max + 255) / 256), B), dim3(256), 0, stream, x, (long long)ld_x, y, (long long)ld_y, n_max, start, lens, coef);
+    return unast_check_launch("unast_preemphasis");
 }

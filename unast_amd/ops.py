@@ -1700,6 +1700,53 @@ def trim_bounds(y, lens, top_db, frame_length, hop_length, pad_mode, out=None):
     return out
 
 
+def preemphasis(x, lens, coef, y, start=None):
+    """y[b, start[b] + k] = x[b, start[b] + k] - coef * x[b, start[b] + k - 1] (the raw sample at k = 0) for k < lens[b], numpy's float32
+    result bit for bit (src/utils.py:251); x, y [B, n] distinct, lens / start int32 [B] (start optional: zeros)."""
+    _audio_t("preemphasis", lens, "lens", torch.int32)
+    if start is not None:
+        _audio_t("preemphasis", start, "start", torch.int32, (lens.numel(),))
+    ldx = _rows_2d("preemphasis", x, "x", 1)
+    ldy = _rows_2d("preemphasis", y, "y", 1)
+    if x.shape != y.shape or x.shape[0] != lens.numel():
+        raise ValueError("preemphasis: x and y [B, n >= 1] of one shape, lens [B]")
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("preemphasis: not in place: sample k reads sample k - 1 of the input")
+    check(lib().unast_preemphasis(_p(x), ldx, _p(y), ldy, x.shape[1], _p(start), _p(lens), x.shape[0], coef, _stream()), "unast_preemphasis")
+    return y
+
+
+def features(y, start, samples, T_max, n_fft, hop, win, coef, window, twiddle, basis, ranges, ref_db, max_db, mel, mag, spec=None):
+    """get_spectrograms (src/utils.py:251-276) in one launch: utterance b = y[b, start[b] : start[b] + samples[b]] (start optional) ->
+    mel float32 [B,T_max,n_mels] and mag float32 [B,T_max,1+n_fft/2], normalised, for its 1 + samples[b] // hop frames; spec (complex64, same
+    shape as mag; optional) receives the spectrum of the emphasised signal.  basis float32 [n_mels, 1+n_fft/2], ranges int32 [n_mels, 2]."""
+    _stft_geometry("features", n_fft, hop, win)
+    if hop > win:
+        raise ValueError("features: hop must not exceed win (got hop=%r, win=%r)" % (hop, win))
+    F_ = n_fft // 2 + 1
+    _audio_t("features", samples, "samples", torch.int32)
+    B = samples.numel()
+    if start is not None:
+        _audio_t("features", start, "start", torch.int32, (B,))
+    ld = _rows_2d("features", y, "y", n_fft // 2 + 1)
+    if y.shape[0] != B:
+        raise ValueError("features: y has %d rows, samples %d" % (y.shape[0], B))
+    _audio_t("features", basis, "basis", _F32)
+    if basis.dim() != 2 or basis.shape[0] < 1 or basis.shape[1] != F_:
+        raise ValueError("features: basis must be [n_mels >= 1, %d] (got %s)" % (F_, tuple(basis.shape)))
+    n_mels = basis.shape[0]
+    _audio_t("features", ranges, "ranges", torch.int32, (n_mels, 2))
+    _audio_t("features", window, "window", _F32, (win,))
+    _audio_t("features", twiddle, "twiddle", _C64, (n_fft,))
+    _audio_t("features", mel, "mel", _F32, (B, T_max, n_mels))
+    _audio_t("features", mag, "mag", _F32, (B, T_max, F_))
+    if spec is not None:
+        _audio_t("features", spec, "spec", _C64, (B, T_max, F_))
+    check(lib().unast_features(_p(y), ld, y.shape[1], _p(start), _p(samples), B, T_max, n_fft, hop, win, coef, _p(window), _p(twiddle), _p(basis), _p(ranges),
+                               n_mels, ref_db, max_db, _p(mel), _p(mag), _p(spec), _stream()), "unast_features")
+    return mel, mag
+
+
 # ---- optimizer ---------------------------------------------------------------------------------------------
 _MSE_WS = {}
 

@@ -704,6 +704,19 @@ int unast_features(const float* y, int64_t ld_y, int n_max, const int* start, co
 int unast_preemphasis(const float* x, int64_t ld_x, float* y, int64_t ld_y, int n_max, const int* start, const int* lens, int B, float coef,
                       hipStream_t stream);
 
+/* Fast Griffin-Lim, librosa.griffinlim as src/gl_vocoder.py:26 calls it (csrc/audio.hip; DESIGN.md section 5s holds the definition).
+ * unast_stft_momentum: unast_stft with the momentum update in its epilogue.  With e the transform of frame (b, t) and tprev complex64
+ * [B, T_max, 1 + n_fft/2]: c = e - alpha tprev, then tprev <- e and spec <- mag c / (|c| + 1e-16), per bin by one thread.  alpha =
+ * momentum / (1 + momentum) in [0, 0.5); with alpha == 0 (the first iteration, where tprev is zero by definition) tprev is written and not
+ * read, so it may be fresh memory.  mag and tprev must not be NULL, tprev is not spec; everything unast_stft refuses is refused here. */
+int unast_stft_momentum(const float* y, int64_t ld_y, const int* frames, int B, int T_max, int n_fft, int hop, int win, const float* window,
+                        const float* twiddle, const float* mag, float alpha, float* tprev, float* spec, hipStream_t stream);
+/* The random initial phase: X0[b,t,k] = M[b,t,k] * twiddle[m] for t < frames[b], m = h(seed, keys[b], t, k) & (n_fft - 1) with
+ * h = pcg(k + pcg(t + pcg(key + pcg(seed)))), pcg the 32-bit pcg_hash of csrc/common.h; keys uint32 device array [B], one per utterance, so
+ * that a draw does not depend on the utterance's place in a batch.  M float32, X0 complex64 [B, T_max, 1 + n_fft/2]. */
+int unast_gl_random_phase(const float* M, const int* frames, const unsigned int* keys, unsigned int seed, int B, int T_max, int n_fft,
+                          const float* twiddle, float* X0, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

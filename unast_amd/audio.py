@@ -8,7 +8,10 @@ Spectra are frame-major [frames, 1 + n_fft/2], the layout Vocoder.forward produc
 Griffin-Lim iteration is three launches (inverse transforms, overlap-add gather, forward transforms with the phase update in their epilogue);
 the utterances of a batch run side by side and each one's result is bit-identical to running it alone.
 
-`librosa.griffinlim` as gl_vocoder.py calls it (random initial phase, momentum) is not this path and is not built.
+`librosa.griffinlim` as gl_vocoder.py calls it (fast Griffin-Lim: 32 iterations, momentum 0.99, random initial phase) is `griffinlim`, and
+method='librosa' of spectrogram2wav_batch / spectrogram2wav / mel2wav / vocode: the momentum update is a second
+epilogue of the forward transform, the random phase a seeded counter-based draw over the n_fft levels of the twiddle table, so that a run
+can be repeated and tested; the deterministic path stays the default.
 
 The other direction, feature extraction: the reference's get_spectrograms (src/utils.py:235-278 -- load, trim, preemphasis, stft, |S|, mel
 basis, dB, normalise, clip) and prepare_data.py's loop over a folder of wavs, a batch of utterances per launch.  The mel
@@ -200,6 +203,106 @@ def griffin_lim(M, lens=None, params=AudioParams(), n_iter=None, X0=None, return
     return y[0] if single else y
 
 
+GL_METHODS = ("reference", "librosa")
+LIBROSA_N_ITER, LIBROSA_MOMENTUM = 32, 0.99          # librosa.griffinlim's defaults, what src/gl_vocoder.py:26 runs with
+
+
+def _alpha(momentum):
+    """momentum / (1 + momentum) in double, rounded to the float32 the kernel multiplies by."""
+    return float(np.float32(momentum / (1.0 + momentum)))
+
+
+def _check_seed(who, seed):
+    if not 0 <= int(seed) < 1 << 32:
+        raise ValueError("%s: seed must fit 32 bits (got %r)" % (who, seed))
+
+
+def _check_method(who, method, seed):
+    if method not in GL_METHODS:
+        raise ValueError("%s: method is 'reference' (src/utils.py:309-320) or 'librosa' (librosa.griffinlim, src/gl_vocoder.py:26), got %r" % (who, method))
+    _check_seed(who, seed)
+
+
+def _check_keys(who, keys, B):
+    """keys as a list of B uint32 values; by default an utterance's index in the batch."""
+    keys = list(range(B)) if keys is None else [int(k) for k in (keys.tolist() if hasattr(keys, "tolist") else keys)]
+    if len(keys) != B:
+        raise ValueError("%s: %d utterances, %d keys" % (who, B, len(keys)))
+    if any(not 0 <= k < 1 << 32 for k in keys):
+        raise ValueError("%s: a key must fit 32 bits (got %s)" % (who, keys))
+    return keys
+
+
+def _keys_dev(keys, device):
+    return torch.from_numpy(np.array(keys, dtype=np.uint32).view(np.int32)).to(device)
+
+
+def _random_phase(M, X, frames_dev, keys, seed, p):
+    """X = M * exp(i phase), the phase drawn per (seed, key, frame, bin) from the n_fft levels of the twiddle table."""
+    _, tw = _tables(p, M.device)
+    return ops.gl_random_phase(M, frames_dev, _keys_dev(keys, M.device), seed, p.n_fft, tw, X)
+
+
+def _fast_griffin_lim(M, X, tprev, frames_dev, p, n_iter, alpha, y):
+    """librosa.griffinlim's loop on M float32 / X = M * angles0 complex64 [B,T,bins] (overwritten) into y [B, hop (T-1)].  tprev complex64
+    [B,T,bins] is workspace: the first iteration runs with alpha = 0 (tprev = 0 by definition) and does not read it, so it may be fresh memory."""
+    B, T = M.shape[0], M.shape[1]
+    window, tw = _tables(p, M.device)
+    fr = torch.empty(B, T, p.win, dtype=_F32, device=M.device)
+    for i in range(n_iter):
+        _istft_into(X, frames_dev, p, window, tw, fr, y)
+        ops.stft_momentum(y, frames_dev, T, p.n_fft, p.hop, p.win, window, tw, X, M, alpha if i else 0.0, tprev)
+    return _istft_into(X, frames_dev, p, window, tw, fr, y)
+
+
+def griffinlim(S, lens=None, params=AudioParams(), n_iter=LIBROSA_N_ITER, momentum=LIBROSA_MOMENTUM, init="random", seed=0, keys=None, angles0=None,
+               return_state=False):
+    """librosa.griffinlim(S, n_iter, hop_length=hop, win_length=win, momentum=momentum) (src/gl_vocoder.py:26; fast Griffin-Lim, Perraudin et
+    al.) for a frame-major magnitude S (float32, non-negative, [T, bins] or [B, T, bins]): ang = angles0, tprev = 0; n_iter times e =
+    stft(istft(S * ang)), c = e - momentum / (1 + momentum) * tprev, tprev = e, ang = c / (|c| + 1e-16); returns istft(S * ang), float32
+    [hop (T-1)] or [B, hop (T_max-1)].  init: 'random' -- a phase per (seed, key, frame, bin) uniform over n_fft levels, keys one uint32 per
+    utterance (default: its index), so that a draw does not depend on the batch (librosa draws a continuous phase from an unseeded generator) --
+    or None, all phases zero.  angles0 (complex64, S's shape) overrides init.  return_state: (waveform, X, tprev), the last iterate S * ang and
+    the last rebuilt spectrum."""
+    who = "griffinlim"
+    p = params
+    _check_params(who, p)
+    if int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError("%s: n_iter must be a non-negative integer (got %r)" % (who, n_iter))
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError("%s: momentum must lie in [0, 1) (got %r)" % (who, momentum))
+    if angles0 is None and init not in (None, "random"):
+        raise ValueError("%s: init is 'random' or None (got %r)" % (who, init))
+    _check_seed(who, seed)
+    S3, single = _check_spec(who, S, p, False)
+    B, T = S3.shape[0], S3.shape[1]
+    lens = _check_lens(who, [T] * B if lens is None else lens, T, p)
+    if len(lens) != B:
+        raise ValueError("%s: %d utterances, %d lengths" % (who, B, len(lens)))
+    keys = _check_keys(who, keys, B)
+    if angles0 is not None:
+        A3, _ = _check_spec(who, angles0, p, True)
+        if A3.shape != S3.shape:
+            raise ValueError("%s: angles0 and S differ in shape" % who)
+    _need_cuda(who, S3, "S")
+    dev = S3.device
+    M = S3.contiguous()
+    frames_dev = _i32(lens, dev)
+    if angles0 is not None:
+        _need_cuda(who, A3, "angles0")
+        X = (M * A3).contiguous()
+    elif init is None:
+        X = torch.complex(M, torch.zeros_like(M))
+    else:
+        X = _random_phase(M, torch.zeros(B, T, p.bins, dtype=torch.complex64, device=dev), frames_dev, keys, seed, p)
+    tprev = torch.zeros_like(X)
+    y = torch.zeros(B, p.hop * (T - 1), dtype=_F32, device=dev)
+    _fast_griffin_lim(M, X, tprev, frames_dev, p, int(n_iter), _alpha(momentum), y)
+    if return_state:
+        return (y[0], X[0], tprev[0]) if single else (y, X, tprev)
+    return y[0] if single else y
+
+
 def invert_spectrogram(S, params=AudioParams()):
     """src/utils.py:323-328 (frame-major)."""
     return istft(S, None, params)
@@ -231,11 +334,15 @@ def trim_bounds(y, lens=None, top_db=60.0, frame_length=2048, hop_length=512, pa
     return out[0] if single else out
 
 
-def spectrogram2wav_batch(mags, lens, params=AudioParams(), trim=True, pad_mode="reflect"):
+def spectrogram2wav_batch(mags, lens, params=AudioParams(), trim=True, pad_mode="reflect", method="reference", seed=0, keys=None):
     """src/utils.py:281-306 for a batch: mags float32 [B, T, bins] normalised magnitudes (Vocoder.forward's output as it is), lens frames per
-    utterance -> a list of 1-D float32 device tensors, utterance b with at most hop * (lens[b] - 1) samples (fewer after trimming)."""
+    utterance -> a list of 1-D float32 device tensors, utterance b with at most hop * (lens[b] - 1) samples (fewer after trimming).
+    method 'reference': the deterministic iteration of src/utils.py:309-320, params.n_iter times.  method 'librosa': what src/gl_vocoder.py:26
+    runs in its place, griffinlim with 32 iterations, momentum 0.99 and the random phase of (seed, keys) (keys: one uint32 per utterance,
+    default its index in the batch)."""
     p = params
     _check_params("spectrogram2wav_batch", p)
+    _check_method("spectrogram2wav_batch", method, seed)
     if pad_mode not in ("reflect", "constant"):
         raise ValueError("spectrogram2wav_batch: pad_mode is 'reflect' (librosa 0.8) or 'constant' (later versions), got %r" % (pad_mode,))
     if not torch.is_tensor(mags) or mags.dim() != 3:
@@ -246,16 +353,23 @@ def spectrogram2wav_batch(mags, lens, params=AudioParams(), trim=True, pad_mode=
     lens = _check_lens("spectrogram2wav_batch", lens, T, p)
     if len(lens) != B:
         raise ValueError("spectrogram2wav_batch: %d utterances, %d lengths" % (B, len(lens)))
+    if method == "librosa":
+        keys = _check_keys("spectrogram2wav_batch", keys, B)
     _need_cuda("spectrogram2wav_batch", mags, "mags")
     dev = mags.device
     with torch.no_grad():
         T_max = T                                            # frames behind an utterance's length are skipped by every kernel
         M = torch.empty(B, T_max, p.bins, dtype=_F32, device=dev)
         X = torch.empty(B, T_max, p.bins, dtype=torch.complex64, device=dev)
-        ops.gl_prepare(mags, p.max_db, p.ref_db, p.power, M, X)
         frames_dev = _i32(lens, dev)
         y = torch.zeros(B, p.hop * (T_max - 1), dtype=_F32, device=dev)
-        _griffin_lim(M, X, frames_dev, p, p.n_iter, y)
+        if method == "librosa":
+            ops.gl_prepare(mags, p.max_db, p.ref_db, p.power, M)
+            _random_phase(M, X, frames_dev, keys, seed, p)
+            _fast_griffin_lim(M, X, torch.empty_like(X), frames_dev, p, LIBROSA_N_ITER, _alpha(LIBROSA_MOMENTUM), y)
+        else:
+            ops.gl_prepare(mags, p.max_db, p.ref_db, p.power, M, X)
+            _griffin_lim(M, X, frames_dev, p, p.n_iter, y)
         samples = [p.hop * (n - 1) for n in lens]
         samples_dev = _i32(samples, dev)
         ops.deemphasis(y, samples_dev, p.preemphasis, y)
@@ -266,8 +380,9 @@ def spectrogram2wav_batch(mags, lens, params=AudioParams(), trim=True, pad_mode=
         return [y[b, s:e] for b, (s, e) in enumerate(bounds)]
 
 
-def spectrogram2wav(mag, params=AudioParams(), pad_mode="reflect", device="cuda"):
-    """The reference's signature (src/utils.py:281-306): a numpy magnitude [T, 1 + n_fft/2] -> a 1-D float32 numpy waveform."""
+def spectrogram2wav(mag, params=AudioParams(), pad_mode="reflect", device="cuda", method="reference", seed=0):
+    """The reference's signature (src/utils.py:281-306): a numpy magnitude [T, 1 + n_fft/2] -> a 1-D float32 numpy waveform; method and seed
+    as in spectrogram2wav_batch (the utterance's key is 0)."""
     m = torch.as_tensor(np.asarray(mag, dtype=np.float32))
     if m.dim() != 2:
         raise ValueError("spectrogram2wav: mag must be [T, %d]" % params.bins)
@@ -275,17 +390,20 @@ def spectrogram2wav(mag, params=AudioParams(), pad_mode="reflect", device="cuda"
     if m.shape[1] != params.bins:
         raise ValueError("spectrogram2wav: the last dimension must be 1 + n_fft/2 = %d (got %d)" % (params.bins, m.shape[1]))
     _check_lens("spectrogram2wav", [m.shape[0]], m.shape[0], params)
+    _check_method("spectrogram2wav", method, seed)
     if not torch.cuda.is_available():
         raise RuntimeError("spectrogram2wav: needs a CUDA (ROCm) device: the transforms are HIP kernels and have no CPU path")
-    return spectrogram2wav_batch(m.to(device).unsqueeze(0), [m.shape[0]], params, True, pad_mode)[0].cpu().numpy()
+    return spectrogram2wav_batch(m.to(device).unsqueeze(0), [m.shape[0]], params, True, pad_mode, method, seed)[0].cpu().numpy()
 
 
-def mel2wav(vocoder, mel, mel_lens, params=AudioParams(), trim=True, pad_mode="reflect"):
+def mel2wav(vocoder, mel, mel_lens, params=AudioParams(), trim=True, pad_mode="reflect", method="reference", seed=0, keys=None):
     """mel [B, T, num_mels] -> waveforms: Vocoder.forward under no_grad (src/inf_vocoder.py:56-64), then spectrogram2wav_batch (gl_vocoder.py's
-    loop over the stored magnitudes, with the deterministic Griffin-Lim of src/utils.py)."""
+    loop over the stored magnitudes: by default with the deterministic Griffin-Lim of src/utils.py, with method='librosa' with its own
+    librosa.griffinlim)."""
+    _check_method("mel2wav", method, seed)
     with torch.no_grad():
         mags = vocoder.forward(mel)
-    return spectrogram2wav_batch(mags, mel_lens, params, trim, pad_mode)
+    return spectrogram2wav_batch(mags, mel_lens, params, trim, pad_mode, method, seed, keys)
 
 
 def write_wav(path, wav, sr=AudioParams.sr):
@@ -302,9 +420,11 @@ def write_wav(path, wav, sr=AudioParams.sr):
     return path
 
 
-def vocode(names, mags_dir, out_dir, params=AudioParams(), pad_mode="reflect", device="cuda", batch=32):
+def vocode(names, mags_dir, out_dir, params=AudioParams(), pad_mode="reflect", device="cuda", batch=32, method="reference", seed=0):
     """gl_vocoder.py's loop: reads <mags_dir>/<name>.mag.npy (what make_mags' caller stores, [T, bins] each), synthesises `batch` utterances at a
-    time and writes <out_dir>/<name>.wav.  Returns the paths written."""
+    time and writes <out_dir>/<name>.wav.  Returns the paths written.  method='librosa' runs gl_vocoder.py's own algorithm (griffinlim); an
+    utterance's random phase is keyed by its index in names, so one list gives the same files at any `batch`."""
+    _check_method("vocode", method, seed)
     os.makedirs(out_dir, exist_ok=True)
     names = list(names)
     out = []
@@ -315,7 +435,7 @@ def vocode(names, mags_dir, out_dir, params=AudioParams(), pad_mode="reflect", d
         padded = np.zeros((len(mags), max(lens), params.bins), dtype=np.float32)
         for b, m in enumerate(mags):
             padded[b, :lens[b]] = m
-        wavs = spectrogram2wav_batch(torch.from_numpy(padded).to(device), lens, params, True, pad_mode)
+        wavs = spectrogram2wav_batch(torch.from_numpy(padded).to(device), lens, params, True, pad_mode, method, seed, list(range(i, i + len(part))))
         for n, w in zip(part, wavs):
             out.append(write_wav(os.path.join(out_dir, "%s.wav" % n), w, params.sr))
     return out

@@ -110,9 +110,14 @@ __device__ int fft_lds(FftLds& s, const float2* __restrict__ tw, int N) {
 // S[b,t,:] = rfft(wp * yp[t hop : t hop + N]); with mag: mag * S / max(1e-8, |S|) (the Griffin-Lim update, src/utils.py:314-316).
 // The reflect padding is index arithmetic: sample p of the padded signal is y[|p - N/2|] on the left and y[2 (n - 1) - (p - N/2)] on the
 // right; n > N / 2 (checked by the caller through min_frames) makes one reflection enough.  Samples outside the window are zero and not loaded.
+// MOMENTUM: the fast Griffin-Lim update of librosa.griffinlim in the same epilogue: with e = S, c = e - alpha tprev,
+// the thread that owns bin k reads tprev[k], stores tprev[k] <- e and spec[k] <- mag c / (|c| + 1e-16).  alpha == 0 is the first iteration
+// (tprev = 0 by definition) and plain Griffin-Lim: tprev is then not read, so it may be fresh memory.
+template <bool MOMENTUM>
 __global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const float* __restrict__ y, long long ld_y, const int* __restrict__ frames, int T_max, int N,
                                                            int hop, int win, int min_frames, const float* __restrict__ window,
-                                                           const float2* __restrict__ tw, const float* __restrict__ mag, float2* __restrict__ spec) {
+                                                           const float2* __restrict__ tw, const float* __restrict__ mag, float alpha,
+                                                           float2* tprev, float2* __restrict__ spec) {
     __shared__ FftLds s;
     const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
     const int f = min(frames[b], T_max);
@@ -140,7 +145,19 @@ __global__ __launch_bounds__(FFT_THREADS) void stft_kernel(const float* __restri
     for (int k = tid; k < F; k += FFT_THREADS) {
         const int pi = padi(k);
         float re = s.re[cur][pi], im = s.im[cur][pi];
-        if (mag) {
+        if (MOMENTUM) {
+            const float2 e = make_float2(re, im);
+            if (alpha != 0.f) {
+                const float2 tp = tprev[row + k];
+                re = __builtin_fmaf(-alpha, tp.x, re);
+                im = __builtin_fmaf(-alpha, tp.y, im);
+            }
+            tprev[row + k] = e;
+            const float a = sqrtf(__builtin_fmaf(re, re, im * im)) + 1e-16f;
+            const float g = mag[row + k];
+            re = g * re / a;
+            im = g * im / a;
+        } else if (mag) {
             const float a = fmaxf(1e-8f, sqrtf(__builtin_fmaf(re, re, im * im)));
             const float g = mag[row + k];
             re = g * re / a;
@@ -209,6 +226,26 @@ __global__ __launch_bounds__(256) void gl_prepare_kernel(const float* __restrict
         M[i] = v;
         if (X0) X0[i] = make_float2(v, 0.f);
     }
+}
+
+// The phase index of librosa.griffinlim's random start: a counter-based draw from (seed, key, frame, bin), each
+// argument entering under a pcg_hash of its own; tests/fast_griffin_lim_mirror.py restates it in numpy.
+__device__ __forceinline__ uint32_t gl_phase_hash(uint32_t seed, uint32_t key, uint32_t t, uint32_t k) {
+    return pcg_hash(k + pcg_hash(t + pcg_hash(key + pcg_hash(seed))));
+}
+
+// X0[b,t,k] = M[b,t,k] tw[m], m = gl_phase_hash(seed, keys[b], t, k) & (N - 1): a phase uniform over the N levels of the twiddle table.
+__global__ __launch_bounds__(256) void gl_random_phase_kernel(const float* __restrict__ M, const int* __restrict__ frames, const uint32_t* __restrict__ keys,
+                                                              uint32_t seed, int T_max, int N, const float2* __restrict__ tw, float2* __restrict__ X0) {
+    const int b = blockIdx.y, F = (N >> 1) + 1;
+    const int f = min(frames[b], T_max);
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)f * F) return;
+    const int t = (int)(i / F), k = (int)(i - (long long)t * F);
+    const float2 w = tw[gl_phase_hash(seed, keys[b], (uint32_t)t, (uint32_t)k) & (uint32_t)(N - 1)];
+    const size_t o = (size_t)b * T_max * F + (size_t)i;
+    const float g = M[o];
+    X0[o] = make_float2(g * w.x, g * w.y);
 }
 
 // y[k] = x[k] + c y[k-1] (scipy.signal.lfilter([1], [1, -c]), src/utils.py:301) as a blocked scan: one workgroup per utterance walks it in
@@ -430,21 +467,53 @@ int check_stft_params(const char* who, int B, int T_max, int n_fft, int hop, int
     return UNAST_OK;
 }
 
+// What unast_stft and unast_stft_momentum refuse alike; *min_frames: the shortest utterance the kernel transforms.
+int check_stft_call(const char* who, const float* y, int64_t ld_y, const int* frames, int B, int T_max, int n_fft, int hop, int win,
+                    const float* window, const float* twiddle, const float* spec, int* min_frames) {
+    if (int rc = check_stft_params(who, B, T_max, n_fft, hop, win)) return rc;
+    UNAST_REQUIRE(y && frames && window && twiddle && spec, "%s: null pointer", who);
+    *min_frames = n_fft / (2 * hop) + 2;
+    UNAST_REQUIRE(T_max >= *min_frames, "%s: an utterance needs at least n_fft / (2 hop) + 2 = %d frames: the signal must be longer than the reflect padding (T_max=%d)",
+                  who, *min_frames, T_max);
+    UNAST_REQUIRE(ld_y >= (int64_t)hop * (T_max - 1), "%s: the row stride %lld is below hop * (T_max - 1) = %lld samples", who, (long long)ld_y, (long long)hop * (T_max - 1));
+    UNAST_REQUIRE((((uintptr_t)twiddle) & 7) == 0 && (((uintptr_t)spec) & 7) == 0, "%s: twiddle and spec hold complex values and need 8-byte alignment", who);
+    return UNAST_OK;
+}
+
 }  // namespace
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------------
 extern "C" int unast_stft(const float* y, int64_t ld_y, const int* frames, int B, int T_max, int n_fft, int hop, int win, const float* window,
                           const float* twiddle, const float* mag, float* spec, hipStream_t stream) {
-    if (int rc = check_stft_params("unast_stft", B, T_max, n_fft, hop, win)) return rc;
-    UNAST_REQUIRE(y && frames && window && twiddle && spec, "unast_stft: null pointer");
-    const int min_frames = n_fft / (2 * hop) + 2;
-    UNAST_REQUIRE(T_max >= min_frames, "unast_stft: an utterance needs at least n_fft / (2 hop) + 2 = %d frames: the signal must be longer than the reflect padding (T_max=%d)",
-                  min_frames, T_max);
-    UNAST_REQUIRE(ld_y >= (int64_t)hop * (T_max - 1), "unast_stft: the row stride %lld is below hop * (T_max - 1) = %lld samples", (long long)ld_y, (long long)hop * (T_max - 1));
-    UNAST_REQUIRE((((uintptr_t)twiddle) & 7) == 0 && (((uintptr_t)spec) & 7) == 0, "unast_stft: twiddle and spec hold complex values and need 8-byte alignment");
-    hipLaunchKernelGGL(stft_kernel, dim3(T_max, B), dim3(FFT_THREADS), 0, stream, y, (long long)ld_y, frames, T_max, n_fft, hop, win, min_frames, window,
-                       (const float2*)twiddle, mag, (float2*)spec);
+    int min_frames = 0;
+    if (int rc = check_stft_call("unast_stft", y, ld_y, frames, B, T_max, n_fft, hop, win, window, twiddle, spec, &min_frames)) return rc;
+    hipLaunchKernelGGL(stft_kernel<false>, dim3(T_max, B), dim3(FFT_THREADS), 0, stream, y, (long long)ld_y, frames, T_max, n_fft, hop, win, min_frames, window,
+                       (const float2*)twiddle, mag, 0.f, (float2*)nullptr, (float2*)spec);
     return unast_check_launch("unast_stft");
+}
+
+extern "C" int unast_stft_momentum(const float* y, int64_t ld_y, const int* frames, int B, int T_max, int n_fft, int hop, int win, const float* window,
+                                   const float* twiddle, const float* mag, float alpha, float* tprev, float* spec, hipStream_t stream) {
+    int min_frames = 0;
+    if (int rc = check_stft_call("unast_stft_momentum", y, ld_y, frames, B, T_max, n_fft, hop, win, window, twiddle, spec, &min_frames)) return rc;
+    UNAST_REQUIRE(mag && tprev, "unast_stft_momentum: null pointer (mag and tprev are needed)");
+    UNAST_REQUIRE(alpha >= 0.f && alpha < 0.5f, "unast_stft_momentum: alpha = momentum / (1 + momentum) must lie in [0, 0.5) (got %g)", (double)alpha);
+    UNAST_REQUIRE((((uintptr_t)tprev) & 7) == 0 && tprev != spec, "unast_stft_momentum: tprev holds complex values, needs 8-byte alignment and is not spec");
+    hipLaunchKernelGGL(stft_kernel<true>, dim3(T_max, B), dim3(FFT_THREADS), 0, stream, y, (long long)ld_y, frames, T_max, n_fft, hop, win, min_frames, window,
+                       (const float2*)twiddle, mag, alpha, (float2*)tprev, (float2*)spec);
+    return unast_check_launch("unast_stft_momentum");
+}
+
+extern "C" int unast_gl_random_phase(const float* M, const int* frames, const unsigned int* keys, unsigned int seed, int B, int T_max, int n_fft,
+                                     const float* twiddle, float* X0, hipStream_t stream) {
+    if (int rc = check_stft_params("unast_gl_random_phase", B, T_max, n_fft, 1, n_fft)) return rc;
+    UNAST_REQUIRE(M && frames && keys && twiddle && X0, "unast_gl_random_phase: null pointer");
+    UNAST_REQUIRE((((uintptr_t)twiddle) & 7) == 0 && (((uintptr_t)X0) & 7) == 0, "unast_gl_random_phase: twiddle and X0 hold complex values and need 8-byte alignment");
+    const long long per = (long long)T_max * (n_fft / 2 + 1);
+    UNAST_REQUIRE(per < (1ll << 31), "unast_gl_random_phase: T_max * (1 + n_fft / 2) must stay below 2^31 (T_max=%d)", T_max);
+    hipLaunchKernelGGL(gl_random_phase_kernel, dim3((unsigned)((per + 255) / 256), B), dim3(256), 0, stream, M, frames, (const uint32_t*)keys, (uint32_t)seed, T_max,
+                       n_fft, (const float2*)twiddle, (float2*)X0);
+    return unast_check_launch("unast_gl_random_phase");
 }
 
 extern "C" int unast_istft_frames(const float* spec, const int* frames, int B, int T_max, int n_fft, int win, const float* window, const float* twiddle,

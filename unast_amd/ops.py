@@ -1617,6 +1617,50 @@ def stft(y, frames, T_max, n_fft, hop, win, window, twiddle, spec, mag=None):
     return spec
 
 
+def stft_momentum(y, frames, T_max, n_fft, hop, win, window, twiddle, spec, mag, alpha, tprev):
+    """stft with the fast Griffin-Lim update (librosa.griffinlim) in its epilogue: with e the transform, c = e - alpha * tprev, then
+    tprev <- e and spec <- mag * c / (|c| + 1e-16).  tprev complex64 [B,T_max,1+n_fft/2]; alpha = momentum / (1 + momentum) in [0, 0.5);
+    alpha == 0 (the first iteration) does not read tprev."""
+    _stft_geometry("stft_momentum", n_fft, hop, win)
+    F_ = n_fft // 2 + 1
+    _audio_t("stft_momentum", frames, "frames", torch.int32)
+    B = frames.numel()
+    ld = _rows_2d("stft_momentum", y, "y", hop * (T_max - 1))
+    _audio_t("stft_momentum", spec, "spec", _C64, (B, T_max, F_))
+    _audio_t("stft_momentum", tprev, "tprev", _C64, (B, T_max, F_))
+    _audio_t("stft_momentum", mag, "mag", _F32, (B, T_max, F_))
+    _audio_t("stft_momentum", window, "window", _F32, (win,))
+    _audio_t("stft_momentum", twiddle, "twiddle", _C64, (n_fft,))
+    if y.shape[0] != B:
+        raise ValueError("stft_momentum: y has %d rows, frames %d" % (y.shape[0], B))
+    if not 0.0 <= alpha < 0.5:
+        raise ValueError("stft_momentum: alpha = momentum / (1 + momentum) must lie in [0, 0.5) (got %r)" % (alpha,))
+    if tprev.data_ptr() == spec.data_ptr():
+        raise ValueError("stft_momentum: tprev and spec are two buffers")
+    check(lib().unast_stft_momentum(_p(y), ld, _p(frames), B, T_max, n_fft, hop, win, _p(window), _p(twiddle), _p(mag), alpha, _p(tprev), _p(spec), _stream()),
+          "unast_stft_momentum")
+    return spec
+
+
+def gl_random_phase(M, frames, keys, seed, n_fft, twiddle, X0):
+    """X0 complex64 [B,T,1+n_fft/2] = M * twiddle[m] for the frames t < frames[b], m a counter-based draw from (seed, keys[b], t, bin) over the
+    n_fft levels of the twiddle table (include/unast_hip.h writes the function out).  keys: one uint32 per utterance, handed over as an int32 tensor [B] of the same bits."""
+    _stft_geometry("gl_random_phase", n_fft, 1, n_fft)
+    _audio_t("gl_random_phase", frames, "frames", torch.int32)
+    B = frames.numel()
+    _audio_t("gl_random_phase", M, "M", _F32)
+    if M.dim() != 3 or M.shape[0] != B or M.shape[2] != n_fft // 2 + 1:
+        raise ValueError("gl_random_phase: M must be [B, T, %d] with B = len(frames) (got %s)" % (n_fft // 2 + 1, tuple(M.shape)))
+    _audio_t("gl_random_phase", X0, "X0", _C64, M.shape)
+    _audio_t("gl_random_phase", twiddle, "twiddle", _C64, (n_fft,))
+    if not (torch.is_tensor(keys) and keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous() and tuple(keys.shape) == (B,)):
+        raise TypeError("gl_random_phase: keys must be a contiguous int32 CUDA tensor [B] (the uint32 keys' bit patterns)")
+    if not 0 <= int(seed) < 1 << 32:
+        raise ValueError("gl_random_phase: seed must fit 32 bits (got %r)" % (seed,))
+    check(lib().unast_gl_random_phase(_p(M), _p(frames), _p(keys), int(seed), B, M.shape[1], n_fft, _p(twiddle), _p(X0), _stream()), "unast_gl_random_phase")
+    return X0
+
+
 def istft_frames(spec, frames, n_fft, win, window, twiddle, fr):
     """fr float32 [B,T_max,win] = window * irfft(spec[b,t])[(n_fft-win)/2 : (n_fft-win)/2 + win] for t < frames[b]."""
     _stft_geometry("istft_frames", n_fft, 1, win)

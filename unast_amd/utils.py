@@ -173,4 +173,4 @@ def compare_outputs(ground_truth, hypothesis, gt_len, hyp_len):
 # ---------------------------------------------------------------------------------------------------------------
 # Feature extraction (src/utils.py:235-278) and waveform synthesis (:281-328) under the reference's names; spectra are frame-major here (unast_amd/audio.py)
 # ---------------------------------------------------------------------------------------------------------------
-from .audio import get_spectrograms, griffin_lim, invert_spectrogram, spectrogram2wav  # noqa: E402,F401
+from .audio import get_spectrograms, griffin_lim, griffinlim, invert_spectrogram, spectrogram2wav  # noqa: E402,F401

@@ -317,7 +317,7 @@ def compare_with_gated_mirror(sd, mel, mag, loss_type, model, taps, tag):
 @pytest.mark.parametrize("name", FIXTURES)
 def test_step_matches_reference_fixture_and_gated_mirror(golden_dir, name, loss_type):
     """The reference's fixture, then the fp64 mirror under the kernels' own gates.  The forward's contractions run as three split-bf16
-    launches over operand parts (train_vocoder.py: conv_fwd, lin_fwd): with one launch each, the per-tensor gradient bound
+    launches over operand parts (contract.py: conv, linear_rows): with one launch each, the per-tensor gradient bound
     min(1e-3, 16 x e32) was missed at the deepest bank stages (18 .. 21 x e32; tools/vocoder_train_emu.py reproduces that on the CPU from
     the forward products alone).  DESIGN.md section 5g has the figures."""
     from unast_amd.train_vocoder import vocoder_step

@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if "--ddp" in sys.argv:
     os.environ.setdefault("UNAST_DDP_FORCE", "1")          # read when unast_amd.ddp is imported: one rank takes the collective path
 from tests import rnn_weights  # noqa: E402
-from unast_amd import ops, rnn  # noqa: E402
+from unast_amd import contract, ops, rnn  # noqa: E402
 from unast_amd.inference import _capture  # noqa: E402
 from unast_amd.network import TextRNN, SpeechRNN  # noqa: E402
 from unast_amd.portable import synth_batch  # noqa: E402
@@ -175,13 +175,12 @@ def train_decoder_mode():
 
 def prefix_position_loop(P, ids, p, seed, params):
     """The comparator of --train-text-decoder: the prefix prenet's forward and backward issued position by position through the uniform-[B,T]
-    entry points (unast_embed_fwd / _bwd, _conv, unast_bn_fwd / _bwd, the conv gradients) -- the same arithmetic as the slab form, about
+    entry points (unast_embed_fwd / _bwd, contract.conv, unast_bn_fwd / _bwd, the conv gradients) -- the same arithmetic as the slab form, about
     100 launches of a few hundred rows per position.  Timing only: the gradients land in the model's .grad."""
-    from unast_amd import train_rnn as TR
     from unast_amd.utils import SOS_IDX
     Bb, T = ids.shape
     E = P.emb.shape[1]
-    TR._prepare_grads(params, False)
+    contract.prepare_grads(params, False)
     sos = torch.full((Bb, 1), SOS_IDX, dtype=torch.int64, device=D)
     bn_ws = torch.empty(512, dtype=torch.float64, device=D)
     saved = []
@@ -194,7 +193,7 @@ def prefix_position_loop(P, ids, p, seed, params):
         xs, zs, mean, rstd = [x0], [], torch.empty(3, 256, device=D), torch.empty(3, 256, device=D)
         cur = x0.view(Bb, L, E)
         for i, (wp, bias, _, bn) in enumerate(P.convs):
-            z = TR._conv(cur, wp, bias, 2).view(N, 256)
+            z = contract.conv(cur, wp, bias, 2).view(N, 256)
             y = torch.empty(N, 256, device=D)
             ops.bn_fwd(z, bn.weight, bn.bias, y, mean[i], rstd[i], bn.running_mean, bn.running_var, bn_ws, 1, drop_p=p, seed=seed, stream_id=41 + i, eps=bn.eps,
                        momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
@@ -213,7 +212,7 @@ def prefix_position_loop(P, ids, p, seed, params):
             wpair, _, conv, bn = P.convs[i]
             dz = torch.empty(N, 256, device=D)
             ops.bn_bwd(dy, zs[i], mean[i], rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 1, drop_p=p, seed=seed, stream_id=41 + i)
-            dy = TR._conv_grads(dz, xs[i], Bb, L, wpair, conv, 2)
+            dy = contract.conv_grads(dz, xs[i], Bb, L, wpair, conv, 2)
         ops.embed_bwd(tok, dy, P.emb_grad, L, drop_p=p, seed=seed, stream_id=40, padding_idx=0)
 
 
@@ -266,7 +265,7 @@ def train_text_decoder_mode():
             if attn == "luong":
                 P = train_rnn.decoder_pack_of(tm, train_rnn.TextDecoderPack)
                 params = list(tm.prenet.parameters())
-                train_rnn._prepare_grads(params, False)
+                contract.prepare_grads(params, False)
                 P.emb_grad = tm.prenet.embed.weight.grad
                 p = float(tm.prenet.p)
                 loop = median_ms(lambda: prefix_position_loop(P, text, p, 3, params), reps=3)
@@ -333,7 +332,6 @@ def train_cm_mode():
     from collections import defaultdict
     from types import SimpleNamespace
     from unast_amd import train, train_rnn, train_rnn_step
-    from unast_amd.rnn import _conv
     from unast_amd.utils import SOS_IDX, EOS_IDX
     train.DEVICE = D
     cfgs = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "rnn_configs.json")))
@@ -386,7 +384,7 @@ def train_cm_mode():
                         ops.embed_fwd(ids, P.emb, x, L, drop_p=p, seed=1, stream_id=21)
                         cur = x.view(Bb, L, -1)
                         for k, (wp, bias, _, bn) in enumerate(P.convs):
-                            z = _conv(cur, wp, bias, 2)
+                            z = contract.conv(cur, wp, bias, 2)
                             y = torch.empty(N, 256, device=D)
                             ops.bn_fwd(z.view(N, 256), bn.weight, bn.bias, y, mean, rstd, bn.running_mean, bn.running_var, bn_ws, 1, drop_p=p, seed=1,
                                        stream_id=22 + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)

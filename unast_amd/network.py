@@ -557,10 +557,10 @@ class TextRNN(_RNNModel):
         return g.logits[:, None, :g.V].clone(), (g.core.h, g.core.c)
 
     def postprocess(self, dec_output, distrib=False):
-        from . import rnn
+        from . import contract
         P = self._pack()
         shp = dec_output.shape
-        y = rnn._linear_rows(dec_output.detach().reshape(-1, shp[-1]).contiguous(), P.head_rows, P.head[1]).view(*shp[:-1], -1)
+        y = contract.linear_rows(dec_output.detach().reshape(-1, shp[-1]).contiguous(), P.head_rows, P.head[1]).view(*shp[:-1], -1)
         return torch.log_softmax(y, dim=-1) if distrib else y
 
     def infer_sequence(self, enc_outputs, enc_ctxt_mask, max_len=300):

@@ -10,27 +10,19 @@ rule off.  What the kernels read is a derived, cached copy of the parameters (`P
 moves: eval BatchNorm folded into tap-major conv weights, W_ih of both encoder directions as one matrix, W_hh in MFMA fragment order,
 [linear_project | stop_linear] as one head, and beside each GEMM / conv weight the residual the split-bf16 operand preparation drops.
 The train packs of unast_amd.train_rnn derive the same operands through the extractors in front of `Pack` and live in the same version-keyed
-cache (`cached_operands`, one slot of PACK_SLOTS per pack); each pack adds only what its own kernels read.
+cache (`contract.cached_operands`, one slot of PACK_SLOTS per pack); each pack adds only what its own kernels read.
 Every contraction keeps fp32-level products (greedy trajectories are held to the reference's own fp32 error): unast_rnn_linear for the few rows of a
-step, the three-launch split form (_linear_rows, _conv) around the many-row GEMMs and convs.
+step, the three-launch split form (unast_amd.contract: linear_rows, conv) around the many-row GEMMs and convs.
 """
 import torch
 
-from . import ops
+from . import contract, ops
+from .contract import buf, detached
 from .inference import _Generation, _exit_step
 from .utils import SOS_IDX, EOS_IDX, PAD_IDX
-from .vocoder import _fold_bn
 
 _F32 = torch.float32
 WINDOW = 7            # prefix positions the last position of three 5-tap convs depends on (src/network.py:573)
-
-
-def _buf(*shape, dev):
-    return torch.empty(*shape, dtype=_F32, device=dev)
-
-
-def _c(t):
-    return t.detach().contiguous()
 
 
 # ---- what the eval pack and the train packs (unast_amd.train_rnn) derive alike: each function returns the common part, a pack adds its own --------
@@ -45,12 +37,12 @@ def encoder_layers(enc):
         dirs = [tuple(getattr(enc.rnn, "%s_l%d%s" % (n, l, s)) for n in LSTM_NAMES) for s in ("", "_reverse")]
         w_ih, w_hh, b_ih, b_hh = zip(*dirs)
         whh = torch.stack(w_hh)
-        yield dirs, (_resid(torch.cat(w_ih)), ops.lstm_whh_fragments(whh), torch.cat(b_ih).detach().contiguous(), torch.cat(b_hh).detach().contiguous()), whh
+        yield dirs, (contract.resid(torch.cat(w_ih)), ops.lstm_whh_fragments(whh), torch.cat(b_ih).detach().contiguous(), torch.cat(b_hh).detach().contiguous()), whh
 
 
 def encoder_reduce(enc):
     """reduce_h_W, reduce_c_W as (weight, bias, module)."""
-    return [(_c(lin.weight), _c(lin.bias), lin) for lin in (enc.reduce_h_W, enc.reduce_c_W)]
+    return [(detached(lin.weight), detached(lin.bias), lin) for lin in (enc.reduce_h_W, enc.reduce_c_W)]
 
 
 def attention_operands(dec):
@@ -63,8 +55,8 @@ def attention_operands(dec):
     else:
         mode, mods = ops.ATTN_LUONG, (at.project_hid, at.project_eo, at.fc2, None, None)
     q, mem, v, conv, dense = mods
-    return dict(mode=mode, Wq=_c(q.weight), Wmem=_resid(mem.weight), v=_c(v.weight).view(-1), conv_w=_c(conv.weight) if conv is not None else None,
-                dense_w=_c(dense.weight) if dense is not None else None), mods
+    return dict(mode=mode, Wq=detached(q.weight), Wmem=contract.resid(mem.weight), v=detached(v.weight).view(-1), conv_w=detached(conv.weight) if conv is not None else None,
+                dense_w=detached(dense.weight) if dense is not None else None), mods
 
 
 def text_prenet_stages(pn):
@@ -77,14 +69,9 @@ def speech_postnet_stages(po):
     return [(po.conv1.conv, po.pre_batchnorm)] + [(c.conv, bn) for c, bn in zip(po.conv_list, po.batch_norm_list)]
 
 
-def tap_major(conv):
-    """A Conv1d's weight as the tap kernels read it ([Cout, taps, Cin]) with its residual, and its bias."""
-    return _resid(conv.weight.detach().permute(0, 2, 1)), _c(conv.bias)
-
-
 def speech_prenet_linears(prenet):
     """SpeechPrenet's fc1, fc2 as (weight with its residual, bias, module)."""
-    return [(_resid(fc.linear_layer.weight), _c(fc.linear_layer.bias), fc.linear_layer) for fc in (prenet.layer.fc1, prenet.layer.fc2)]
+    return [(contract.resid(fc.linear_layer.weight), detached(fc.linear_layer.bias), fc.linear_layer) for fc in (prenet.layer.fc1, prenet.layer.fc2)]
 
 
 def padded_head(*linears):
@@ -92,7 +79,7 @@ def padded_head(*linears):
     (((Wh, its residual), bh), ldh)."""
     W, b = (torch.cat([getattr(lin, n).detach() for lin in linears]) for n in ("weight", "bias"))
     pad = -W.shape[0] % 4
-    return (_resid(torch.nn.functional.pad(W, (0, 0, 0, pad))), torch.nn.functional.pad(b, (0, pad))), W.shape[0] + pad
+    return (contract.resid(torch.nn.functional.pad(W, (0, 0, 0, pad))), torch.nn.functional.pad(b, (0, pad))), W.shape[0] + pad
 
 
 class Pack:
@@ -103,14 +90,14 @@ class Pack:
             enc, dec = m.encoder, m.decoder
             self.enc = [operands for _, operands, _ in encoder_layers(enc)]
             self.reduce_h, self.reduce_c = ((w, b) for w, b, _ in encoder_reduce(enc))
-            self.dec = [tuple(_c(getattr(dec.rnn, n + "_l%d" % l)) for n in LSTM_NAMES) for l in range(dec.num_layers)]
+            self.dec = [tuple(detached(getattr(dec.rnn, n + "_l%d" % l)) for n in LSTM_NAMES) for l in range(dec.num_layers)]
             vars(self).update(attention_operands(dec)[0])              # mode, Wq, Wmem, v, conv_w, dense_w
-            self.proj = (_c(dec.linear_projection.linear_layer.weight), _c(dec.linear_projection.linear_layer.bias))
+            self.proj = (detached(dec.linear_projection.linear_layer.weight), detached(dec.linear_projection.linear_layer.bias))
             if side == "text":
-                self.emb = _c(m.prenet.embed.weight)
+                self.emb = detached(m.prenet.embed.weight)
                 self.convs = [_fold_resid(conv, bn) for conv, bn in text_prenet_stages(m.prenet)]
-                self.head = (_c(m.postnet.fc1.weight), _c(m.postnet.fc1.bias))
-                self.head_rows = _resid(m.postnet.fc1.weight)
+                self.head = (detached(m.postnet.fc1.weight), detached(m.postnet.fc1.bias))
+                self.head_rows = contract.resid(m.postnet.fc1.weight)
             else:
                 po = m.postnet
                 (self.fc1_rows, b1, _), (self.fc2_rows, b2, _) = speech_prenet_linears(m.prenet)
@@ -118,30 +105,20 @@ class Pack:
                 self.head = (torch.cat([po.linear_project.weight, po.stop_linear.weight]).contiguous(),
                              torch.cat([po.linear_project.bias, po.stop_linear.bias]).contiguous())
                 self.post = [_fold_resid(conv, bn) for conv, bn in speech_postnet_stages(po)]
-                self.post_out = tap_major(po.conv2.conv)
+                self.post_out = contract.tap_major(po.conv2.conv)
 
 
 def _fold_resid(conv, bn):
-    w, b = _fold_bn(conv, bn)
-    return _resid(w), b
+    w, b = contract.fold_bn(conv, bn)
+    return contract.resid(w), b
 
 
 # ---- the version-keyed caches of derived operands: one slot in a model's __dict__ per pack ---------------------------------------------------
 EVAL_SLOT, ENCODER_TRAIN_SLOT, DECODER_TRAIN_SLOT = PACK_SLOTS = ("_rnn_pack", "_rnn_train_pack", "_rnn_decoder_train_pack")
 
 
-def cached_operands(m, slot, tensors, build):
-    """m's pack in `slot`, built by build() and rebuilt when the version counter of one of `tensors` has moved (or the device changed)."""
-    key = (sum(t._version for t in tensors), tensors[-1].device if tensors else None)
-    cached = m.__dict__.get(slot)
-    if cached is None or cached[0] != key:
-        cached = (key, build())
-        m.__dict__[slot] = cached
-    return cached[1]
-
-
 def pack_of(m, side):
-    return cached_operands(m, EVAL_SLOT, list(m.parameters()) + list(m.buffers()), lambda: Pack(m, side))
+    return contract.cached_operands(m, EVAL_SLOT, list(m.parameters()) + list(m.buffers()), lambda: Pack(m, side))
 
 
 def drop_eval_pack(m):
@@ -150,67 +127,20 @@ def drop_eval_pack(m):
     m.__dict__.pop(EVAL_SLOT, None)
 
 
-def _resid(w):
-    """(w, what the GEMM's split-bf16 operand preparation drops of w): the weight pair of the fp32-level contractions below."""
-    w = w.detach().contiguous()
-    wr = torch.empty_like(w)
-    ops.split_parts(w, resid=wr)
-    return w, wr
-
-
-def _relu_(x):
-    ops.leaky_dropout(x, None, x, 0.0)
-    return x
-
-
-def _linear_rows(x2d, Wp, b, act=0):
-    """y = act(x W^T + b) for many rows with fp32-level products, Wp = _resid(W): the GEMM's three-term split-bf16 form drops x_lo W_lo and
-    what lies below 2^-17 of either operand; with x = hi + rest (hi exactly bf16) and W = W_hi + W_lo + wr, the three launches
-    hi W + rest W + x wr hold every product but the ones of order 2^-26 (the form unast_amd.train_vocoder uses)."""
-    W, Wr = Wp
-    M, K = x2d.shape
-    N = W.shape[0]
-    dev = x2d.device
-    x = x2d.contiguous()
-    xh, xr = torch.empty_like(x), torch.empty_like(x)
-    ops.split_parts(x, hi=xh, rest=xr)
-    t1, t2, y = _buf(M, N, dev=dev), _buf(M, N, dev=dev), _buf(M, N, dev=dev)
-    ops.gemm(ops.OP_KC, ops.OP_KC, xh, K, W, K, t1, N, M, N, K, bias=b)
-    ops.gemm(ops.OP_KC, ops.OP_KC, xr, K, W, K, t2, N, M, N, K, R=t1, ldr=N)
-    ops.gemm(ops.OP_KC, ops.OP_KC, x, K, Wr, K, y, N, M, N, K, R=t2, ldr=N)
-    return _relu_(y) if act else y
-
-
-def _conv(x3d, Wp, b, pad_left, out=None, work=None):
-    """out = conv(x, W) + b (no activation) with fp32-level products, Wp = _resid(tap-major W); see _linear_rows.  `work`: the four
-    temporaries (x's two parts [B,T,Cin], two partial sums [B,T,Cout]) of a caller that runs the same shape every step."""
-    W, Wr = Wp
-    B, T, _ = x3d.shape
-    dev = x3d.device
-    x = x3d.contiguous()
-    xh, xr, za, zb = work if work is not None else (torch.empty_like(x), torch.empty_like(x), _buf(B, T, W.shape[0], dev=dev), _buf(B, T, W.shape[0], dev=dev))
-    ops.split_parts(x, hi=xh, rest=xr)
-    out = out if out is not None else _buf(B, T, W.shape[0], dev=dev)
-    ops.conv_taps_fwd(xh, W, b, za, pad_left)
-    ops.conv_taps_fwd(xr, W, None, zb, pad_left, R=za)
-    ops.conv_taps_fwd(x, Wr, None, out, pad_left, R=zb)
-    return out
-
-
 # ---- encoders ---------------------------------------------------------------------------------------------------------------------------
 def text_frontend(P, text, noise=None):
     """TextPrenet over whole sequences (src/module.py:217-230, eval): embedding, three conv + BatchNorm + ReLU stages.  [B,T] -> [B,T,256].
     noise = (p, seed, stream): noise_fn on the embedded ids (src/network.py:519-521; it does not look at model.training, so evaluate() keeps it:
     unast_amd.eval_rnn); None changes nothing."""
     B, T = text.shape
-    x = _buf(B * T, P.emb.shape[1], dev=text.device)
+    x = buf(B * T, P.emb.shape[1], dev=text.device)
     if noise is None:
         ops.embed_fwd(text, P.emb, x, T)
     else:
         ops.embed_fwd(text, P.emb, x, T, seed=noise[1], noise_p=noise[0], noise_stream=noise[2])
     x = x.view(B, T, -1)
     for wp, b in P.convs:
-        x = _relu_(_conv(x, wp, b, 2))
+        x = contract.relu_(contract.conv(x, wp, b, 2))
     return x
 
 
@@ -223,8 +153,8 @@ def speech_frontend(P, mel, noise=None):
         mn = torch.empty_like(m2)
         ops.rowmask(m2.contiguous(), mn, noise[0], noise[1], noise[2])
         m2 = mn
-    h = _linear_rows(m2, P.fc1_rows, P.fc1[1], act=1)
-    return _linear_rows(h, P.fc2_rows, P.fc2[1], act=1).view(B, T, -1)
+    h = contract.linear_rows(m2, P.fc1_rows, P.fc1[1], act=1)
+    return contract.linear_rows(h, P.fc2_rows, P.fc2[1], act=1).view(B, T, -1)
 
 
 def encoder(P, x, lens_i32):
@@ -234,10 +164,10 @@ def encoder(P, x, lens_i32):
     dev = x.device
     x2 = x.reshape(B * T, -1)
     L = len(P.enc)
-    h, c = _buf(L, B, 256, dev=dev), _buf(L, B, 256, dev=dev)
+    h, c = buf(L, B, 256, dev=dev), buf(L, B, 256, dev=dev)
     for l, (w_ih, wfrag, b_ih, b_hh) in enumerate(P.enc):
-        xproj = _linear_rows(x2, w_ih, None).view(B, T, -1)
-        y, hn, cn = _buf(B, T, 512, dev=dev), _buf(B, 512, dev=dev), _buf(B, 512, dev=dev)
+        xproj = contract.linear_rows(x2, w_ih, None).view(B, T, -1)
+        y, hn, cn = buf(B, T, 512, dev=dev), buf(B, 512, dev=dev), buf(B, 512, dev=dev)
         ops.lstm_seq_fwd(xproj, wfrag, b_ih, b_hh, lens_i32, y, hn, cn)
         ops.rnn_linear(hn, P.reduce_h[0], P.reduce_h[1], h[l])
         ops.rnn_linear(cn, P.reduce_c[0], P.reduce_c[1], c[l])
@@ -254,12 +184,12 @@ class _Core:
         dev = enc.device
         self.P, self.enc, self.lens_k, self.B = P, enc, lens_k, B
         A = P.Wmem[0].shape[0]
-        self.mem = _linear_rows(enc.view(B * Tk, -1), P.Wmem, None).view(B, Tk, A)       # memory-side projection, once per generation
+        self.mem = contract.linear_rows(enc.view(B * Tk, -1), P.Wmem, None).view(B, Tk, A)  # memory-side projection, once per generation
         self.h0, self.c0 = h0, c0
         self.h, self.c = h0.clone(), c0.clone()
-        self.ctx = _buf(B, 512, dev=dev)
-        self.ga, self.gb = _buf(B, 1024, dev=dev), _buf(B, 1024, dev=dev)
-        self.pa, self.out = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+        self.ctx = buf(B, 512, dev=dev)
+        self.ga, self.gb = buf(B, 1024, dev=dev), buf(B, 1024, dev=dev)
+        self.pa, self.out = buf(B, 256, dev=dev), buf(B, 256, dev=dev)
         if P.mode == ops.ATTN_LSA:
             self.prev, self.cum = lsa_state if lsa_state is not None else (torch.zeros(B, Tk, dtype=_F32, device=dev), torch.zeros(B, Tk, dtype=_F32, device=dev))
         else:
@@ -301,7 +231,7 @@ def _prep(enc_outputs, lens_k):
 def window_bufs(P, B, dev):
     """What text_prenet_last writes: the embedded window, the three conv outputs, and the convs' four temporaries (all [B,7,256], allocated
     once per generation like the rest of the step's state)."""
-    return tuple(_buf(B, WINDOW, P.emb.shape[1], dev=dev) for _ in range(8))
+    return tuple(buf(B, WINDOW, P.emb.shape[1], dev=dev) for _ in range(8))
 
 
 def text_prenet_last(P, tokens, pos_t, teacher_forced, bufs):
@@ -311,11 +241,11 @@ def text_prenet_last(P, tokens, pos_t, teacher_forced, bufs):
     x0, a1, a2, a3 = bufs[:4]
     work = bufs[4:]
     ops.text_window(tokens, P.emb, x0, pos_t, teacher_forced, SOS_IDX)
-    _relu_(_conv(x0, P.convs[0][0], P.convs[0][1], 2, out=a1, work=work))
+    contract.relu_(contract.conv(x0, P.convs[0][0], P.convs[0][1], 2, out=a1, work=work))
     ops.window_mask(a1, pos_t, teacher_forced)
-    _relu_(_conv(a1, P.convs[1][0], P.convs[1][1], 2, out=a2, work=work))
+    contract.relu_(contract.conv(a1, P.convs[1][0], P.convs[1][1], 2, out=a2, work=work))
     ops.window_mask(a2, pos_t, teacher_forced)
-    _relu_(_conv(a2, P.convs[2][0], P.convs[2][1], 2, out=a3, work=work))
+    contract.relu_(contract.conv(a2, P.convs[2][0], P.convs[2][1], 2, out=a3, work=work))
     return a3[:, WINDOW - 1, :]
 
 
@@ -377,9 +307,9 @@ def speech_postnet_sum(P, outs):
     dev = outs.device
     x = outs
     for wp, b in P.post:
-        x = _conv(x, wp, b, 4)
+        x = contract.conv(x, wp, b, 4)
         ops.tanh_rows(x.view(B * T, -1))
-    y = _conv(x, P.post_out[0], P.post_out[1], 4)
+    y = contract.conv(x, P.post_out[0], P.post_out[1], 4)
     ops.add_inplace(y, outs.contiguous())
     return y
 
@@ -408,7 +338,7 @@ def speech_generation(P, enc_outputs, lens_k, max_len, target=None, frame=None, 
     rule_lens = torch.full((B,), max_len, dtype=torch.int64, device=dev) if tf else stop_lens
     pos_t = torch.zeros(1, dtype=torch.int64, device=dev)
     head = torch.zeros(B, ldh, dtype=_F32, device=dev)
-    p1, pre = _buf(B, P.fc1[0].shape[0], dev=dev), _buf(B, 256, dev=dev)
+    p1, pre = buf(B, P.fc1[0].shape[0], dev=dev), buf(B, 256, dev=dev)
 
     def reset():
         pos_t.zero_()

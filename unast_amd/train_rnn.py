@@ -9,8 +9,8 @@ Arithmetic as the reference's train mode: dropout at every nn.Dropout of the pre
 'dropout2' key replaces the first in the OrderedDict, src/module.py:95-102), nn.LSTM's inter-layer dropout on layer 0's output, noise_fn on
 the embedded text / the mel, and BatchNorm on batch statistics over all B*T positions with the running statistics updated.  Masks come
 from the package's counter-based RNG; the tape lists every site (name, p, seed, stream, epoch, rows, cols, kind) so that a test can rebuild
-them (tests/dropout_mirror.py).  Contractions keep fp32-level products in both directions (unast_amd.rnn._linear_rows and its gradient
-forms below).  The recurrence and its backward are unast_lstm_seq_fwd_train / unast_lstm_seq_bwd (csrc/rnn.hip); dW_ih, dW_hh, dx and the
+them (tests/dropout_mirror.py).  Contractions keep fp32-level products in both directions (unast_amd.contract: linear_rows and its gradient
+forms).  The recurrence and its backward are unast_lstm_seq_fwd_train / unast_lstm_seq_bwd (csrc/rnn.hip); dW_ih, dW_hh, dx and the
 bias gradients are GEMMs and column sums over the kernel's dxproj.  Everything runs under torch.no_grad() on the current stream.  DESIGN 5i.
 
 SpeechRNN's decoder trains through two more entry points with the same conventions (the second half of this file):
@@ -22,7 +22,7 @@ so that the speech autoencoder is encoder_forward -> decoder_forward -> decoder_
 
 TextRNN's decoder trains through the last pair (the end of this file); both decoders run the same position loop
 (_loop_forward / _loop_backward), each supplying its own prenet rows and head.  The packs (TrainPack for the encoders, DecoderPack /
-TextDecoderPack over _LoopPack for the decoders) are built from unast_amd.rnn's extractors and cached by its cached_operands:
+TextDecoderPack over _LoopPack for the decoders) are built from unast_amd.rnn's extractors and cached by contract.cached_operands:
 
     tape = text_decoder_forward(model, target, enc_outputs, lens_k, seed=0) # tape.logits [B,T,len(symbols)], tape.sites
     d_enc_output, d_h, d_c = text_decoder_backward(tape, d_logits)          # writes p.grad of model.prenet, model.decoder, model.postnet
@@ -37,8 +37,8 @@ import collections
 
 import torch
 
-from . import ops, rnn
-from .rnn import _buf, _c, _conv, _linear_rows, _resid
+from . import contract, ops, rnn
+from .contract import ALL, buf, detached
 from .utils import EOS_IDX, PAD_IDX, SOS_IDX
 
 _F32 = torch.float32
@@ -58,14 +58,14 @@ class TrainPack:
                        for dirs, (w_ih, wfrag, b_ih, b_hh), whh in rnn.encoder_layers(m.encoder)]
         self.reduce = [(w, b, lin.weight.detach().t().contiguous(), lin) for w, b, lin in rnn.encoder_reduce(m.encoder)]
         if side == "text":
-            self.emb = _c(m.prenet.embed.weight)
-            self.convs = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(m.prenet)]   # (tap-major weight pair, bias, conv, bn)
+            self.emb = detached(m.prenet.embed.weight)
+            self.convs = [contract.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(m.prenet)]  # (tap-major weight pair, bias, conv, bn)
         else:
             self.fcs = rnn.speech_prenet_linears(m.prenet)
 
 
 def train_pack_of(m, side):
-    return rnn.cached_operands(m, rnn.ENCODER_TRAIN_SLOT, _encoder_params(m), lambda: TrainPack(m, side))
+    return contract.cached_operands(m, rnn.ENCODER_TRAIN_SLOT, _encoder_params(m), lambda: TrainPack(m, side))
 
 
 class Tape:
@@ -90,46 +90,6 @@ def _check_model(model, what):
         raise TypeError("%s: model must be a unast_amd.network.TextRNN or SpeechRNN" % what)
     if not model.training:
         raise RuntimeError("%s is the train-mode entry point: call model.train() first (model.encode() is the eval forward)" % what)
-
-
-# ---- fp32-level gradient contractions (the forward's three-launch form, unast_amd.rnn._linear_rows) ------------------------------------
-def _parts(x2d):
-    x = x2d.contiguous()
-    hi, rest = torch.empty_like(x), torch.empty_like(x)
-    ops.split_parts(x, hi=hi, rest=rest)
-    return x, hi, rest
-
-
-def _dgrad_rows(dyp, Wp, dx):
-    """dx[M,K] = dy[M,N] W[N,K]; dyp = _parts(dy), Wp = _resid(W)."""
-    dy, dyh, dyr = dyp
-    W, Wr = Wp
-    t1, t2 = torch.empty_like(dx), torch.empty_like(dx)
-    ops.linear_dgrad(dyh, W, t1)
-    ops.linear_dgrad(dyr, W, t2, R=t1)
-    ops.linear_dgrad(dy, Wr, dx, R=t2)
-    return dx
-
-
-def _wgrad_rows(dyp, cols, x2d, xres, dW, dbs=()):
-    """dW[N,K] += dy[:, cols]^T x, every db += column sums of dy[:, cols]; dyp = _parts(dy), xres = what the operand preparation drops of x."""
-    dy, dyh, dyr = (t[:, cols] for t in dyp)
-    M, N = dy.shape
-    K = x2d.shape[1]
-    sk = ops._splitk_for(N, K, M)
-    for a, b in ((dyh, x2d), (dyr, x2d), (dy, xres)):
-        ops.gemm(ops.OP_RC, ops.OP_RC, a, a.stride(0), b, b.stride(0), dW, dW.stride(0), N, K, M, beta=1, splitk=sk)
-    for db in dbs:
-        ops.colsum(dy, db)
-
-
-def _resid_of(x2d):
-    r = torch.empty_like(x2d)
-    ops.split_parts(x2d, resid=r)
-    return r
-
-
-ALL = slice(None)
 
 
 # ---- forward -------------------------------------------------------------------------------------------------------------------------------
@@ -158,7 +118,7 @@ def encoder_forward(model, x, lens, noise_in=False, seed=0):
         B, T = ids.shape
         N = B * T
         p = float(model.prenet.p)
-        x0 = _buf(N, P.emb.shape[1], dev=dev)
+        x0 = buf(N, P.emb.shape[1], dev=dev)
         ops.embed_fwd(ids, P.emb, x0, T, drop_p=p, seed=seed, stream_id=S_EMB, noise_p=noise_p, noise_stream=S_NOISE)
         tape.site("emb_dropout", p, S_EMB, N, x0.shape[1])
         tape.site("noise", noise_p, S_NOISE, N, 1, "row")
@@ -177,25 +137,25 @@ def encoder_forward(model, x, lens, noise_in=False, seed=0):
             m2 = mn
         tape.site("noise", noise_p, S_NOISE, N, 1, "row")
         (w1, b1, _), (w2, b2, _) = P.fcs
-        a1 = _linear_rows(m2, w1, b1)
+        a1 = contract.linear_rows(m2, w1, b1)
         h1 = torch.empty_like(a1)
         ops.leaky_dropout(a1, None, h1, 0.0, p, seed, S_PRE1)
         tape.site("dropout2", p, S_PRE1, N, a1.shape[1])
-        h2 = _linear_rows(h1, w2, b2, act=1)
+        h2 = contract.linear_rows(h1, w2, b2, act=1)
         tape.m2, tape.a1, tape.h1, tape.h2 = m2, a1, h1, h2
         tape.pad_mask = torch.arange(T, device=dev)[None, :] >= lens_i32[:, None]
         front = h2
     # ---- RNNEncoder.forward: packed bidirectional LSTM stack, inter-layer dropout, reduce_h_W / reduce_c_W ------------------------------------
     e_drop = float(model.encoder.rnn.dropout)
     L = len(P.layers)
-    h, c = _buf(L, B, 256, dev=dev), _buf(L, B, 256, dev=dev)
+    h, c = buf(L, B, 256, dev=dev), buf(L, B, 256, dev=dev)
     tape.B, tape.T, tape.e_drop = B, T, e_drop
     tape.lstm = []
     x2 = front
     for l, lay in enumerate(P.layers):
-        xproj = _linear_rows(x2, lay["w_ih"], None).view(B, T, -1)
-        y, hn, cn = _buf(B, T, 512, dev=dev), _buf(B, 512, dev=dev), _buf(B, 512, dev=dev)
-        saved, hprev = _buf(B, T, 2, 5, 256, dev=dev), _buf(B, T, 512, dev=dev)
+        xproj = contract.linear_rows(x2, lay["w_ih"], None).view(B, T, -1)
+        y, hn, cn = buf(B, T, 512, dev=dev), buf(B, 512, dev=dev), buf(B, 512, dev=dev)
+        saved, hprev = buf(B, T, 2, 5, 256, dev=dev), buf(B, T, 512, dev=dev)
         ops.lstm_seq_fwd_train(xproj, lay["wfrag"], lay["b_ih"], lay["b_hh"], lens_i32, y, hn, cn, saved, hprev)
         ops.rnn_linear(hn, P.reduce[0][0], P.reduce[0][1], h[l])
         ops.rnn_linear(cn, P.reduce[1][0], P.reduce[1][1], c[l])
@@ -211,20 +171,6 @@ def encoder_forward(model, x, lens, noise_in=False, seed=0):
 
 
 # ---- backward ------------------------------------------------------------------------------------------------------------------------------
-def _prepare_grads(params, accumulate):
-    gs = []
-    for p in params:
-        g = p.grad
-        if g is None or not g.is_contiguous() or g.dtype is not _F32 or g.device != p.device or g.data_ptr() % 16:
-            new = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            if accumulate and g is not None:
-                new.copy_(g)
-            g = p.grad = new
-        gs.append(g)
-    if not accumulate:
-        torch._foreach_zero_(gs)
-
-
 def _cot(t, shape, name, dev, what="encoder_backward"):
     if t is None:
         return None
@@ -250,7 +196,7 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
     d_enc_output = _cot(d_enc_output, (B, T, 512), "d_enc_output", dev)
     d_h, d_c = _cot(d_h, (L, B, 256), "d_h", dev), _cot(d_c, (L, B, 256), "d_c", dev)
     tape.used = True
-    _prepare_grads(_encoder_params(model), accumulate)
+    contract.prepare_grads(_encoder_params(model), accumulate)
 
     dy = d_enc_output.view(N, 512) if d_enc_output is not None else torch.zeros(N, 512, dtype=_F32, device=dev)
     for l in range(L - 1, -1, -1):
@@ -261,22 +207,22 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
                 dfin.append(None)
                 continue
             g = d_state[l]                                                                 # [B,256]: the gradient of reduce_*_W's output
-            dfin.append(ops.rnn_linear(g, Wt, None, _buf(B, 512, dev=dev)))                # g W [256,512]
-            _wgrad_rows(_parts(g), ALL, fin, _resid_of(fin), lin.weight.grad, (lin.bias.grad,))
+            dfin.append(ops.rnn_linear(g, Wt, None, buf(B, 512, dev=dev)))                 # g W [256,512]
+            contract.wgrad_rows(contract.parts(g), ALL, fin, contract.resid_of(fin), lin.weight.grad, (lin.bias.grad,))
         if l + 1 < L and tape.e_drop > 0.0:
             dyd = torch.empty_like(dy)
             ops.leaky_dropout(dy, dy, dyd, 1.0, tape.e_drop, seed, S_EDROP + l)            # slope 1: the mask and its 1/(1-p) only
             dy = dyd
-        dxproj = _buf(B, T, 2048, dev=dev)
+        dxproj = buf(B, T, 2048, dev=dev)
         ops.lstm_seq_bwd(dy.view(B, T, 512), lay["wfrag_t"], st["saved"], tape.lens, dxproj, dhfinal=dfin[0], dcfinal=dfin[1])
-        dxp = _parts(dxproj.view(N, 2048))
+        dxp = contract.parts(dxproj.view(N, 2048))
         xin, hprev = st["x"], st["hprev"].view(N, 512)
-        xin_res, hprev_res = _resid_of(xin), _resid_of(hprev)
+        xin_res, hprev_res = contract.resid_of(xin), contract.resid_of(hprev)
         for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(lay["params"]):
             cols = slice(1024 * d, 1024 * (d + 1))
-            _wgrad_rows(dxp, cols, xin, xin_res, w_ih.grad, (b_ih.grad, b_hh.grad))
-            _wgrad_rows(dxp, cols, hprev[:, 256 * d:256 * (d + 1)], hprev_res[:, 256 * d:256 * (d + 1)], w_hh.grad)
-        dy = _dgrad_rows(dxp, lay["w_ih"], _buf(N, xin.shape[1], dev=dev))
+            contract.wgrad_rows(dxp, cols, xin, xin_res, w_ih.grad, (b_ih.grad, b_hh.grad))
+            contract.wgrad_rows(dxp, cols, hprev[:, 256 * d:256 * (d + 1)], hprev_res[:, 256 * d:256 * (d + 1)], w_hh.grad)
+        dy = contract.dgrad_rows(dxp, lay["w_ih"], buf(N, xin.shape[1], dev=dev))
 
     if tape.side == "text":
         C = 256
@@ -284,10 +230,10 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
         bn_ws = torch.empty(2 * C, dtype=torch.float64, device=dev)
         for i in (2, 1, 0):
             wpair, _, conv, bn = P.convs[i]
-            dz = _buf(N, C, dev=dev)
+            dz = buf(N, C, dev=dev)
             ops.bn_bwd(dy, tape.zs[i], tape.mean[i], tape.rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 1, drop_p=p, seed=seed,
                        stream_id=S_PRE1 + i)
-            dy = _conv_grads(dz, tape.xs[i], B, T, wpair, conv, 2)
+            dy = contract.conv_grads(dz, tape.xs[i], B, T, wpair, conv, 2)
         noise_p = NOISE_P if tape.noise_in else 0.0
         ops.embed_bwd(tape.ids, dy, model.prenet.embed.weight.grad, T, drop_p=p, seed=seed, stream_id=S_EMB, noise_p=noise_p, noise_stream=S_NOISE,
                       padding_idx=model.prenet.embed.padding_idx)
@@ -296,15 +242,15 @@ def encoder_backward(tape, d_enc_output=None, d_h=None, d_c=None, accumulate=Fal
     p = float(model.prenet.p)
     (w1, _, fc1), (w2, _, fc2) = P.fcs
     ops.relu_bwd(dy, tape.h2)
-    dyp = _parts(dy)
-    _wgrad_rows(dyp, ALL, tape.h1, _resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
-    dh1 = _dgrad_rows(dyp, w2, _buf(N, tape.h1.shape[1], dev=dev))
+    dyp = contract.parts(dy)
+    contract.wgrad_rows(dyp, ALL, tape.h1, contract.resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
+    dh1 = contract.dgrad_rows(dyp, w2, buf(N, tape.h1.shape[1], dev=dev))
     da1 = torch.empty_like(dh1)
     ops.leaky_dropout(tape.a1, dh1, da1, 0.0, p, seed, S_PRE1)
-    dap = _parts(da1)
-    _wgrad_rows(dap, ALL, tape.m2, _resid_of(tape.m2), fc1.weight.grad, (fc1.bias.grad,))
+    dap = contract.parts(da1)
+    contract.wgrad_rows(dap, ALL, tape.m2, contract.resid_of(tape.m2), fc1.weight.grad, (fc1.bias.grad,))
     M = tape.m2.shape[1]
-    d_mel = _dgrad_rows(dap, w1, _buf(N, M, dev=dev))
+    d_mel = contract.dgrad_rows(dap, w1, buf(N, M, dev=dev))
     if tape.noise_in:
         out = torch.empty_like(d_mel)
         ops.rowmask(d_mel, out, NOISE_P, seed, S_NOISE)
@@ -328,9 +274,9 @@ class _LoopPack:
         w0 = r.weight_ih_l0.detach()
         if tuple(w0.shape) != (1024, 768) or tuple(r.weight_ih_l1.shape) != (1024, 256):
             raise NotImplementedError("%s: hidden = e_in = 256 with a 512-wide encoder output" % what)
-        self.w_ih0_p, self.w_ih0_c = _resid(w0[:, :256]), _c(w0[:, 256:])                   # the prenet columns (batched) and the context columns
-        self.w_hh0, self.w_ih1, self.w_hh1 = _c(r.weight_hh_l0), _c(r.weight_ih_l1), _c(r.weight_hh_l1)
-        self.bias = [_c(getattr(r, n)) for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1")]
+        self.w_ih0_p, self.w_ih0_c = contract.resid(w0[:, :256]), detached(w0[:, 256:])     # the prenet columns (batched) and the context columns
+        self.w_hh0, self.w_ih1, self.w_hh1 = detached(r.weight_hh_l0), detached(r.weight_ih_l1), detached(r.weight_hh_l1)
+        self.bias = [detached(getattr(r, n)) for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1")]
         tr = lambda w: w.detach().t().contiguous()                                          # noqa: E731
         self.wt_ihc0, self.wt_hh0, self.wt_ih1, self.wt_hh1 = tr(w0[:, 256:]), tr(r.weight_hh_l0), tr(r.weight_ih_l1), tr(r.weight_hh_l1)
         operands, (self.q_lin, self.mem_lin, self.v_lin, self.conv_mod, self.dense_lin) = rnn.attention_operands(dec)
@@ -339,7 +285,7 @@ class _LoopPack:
         if self.A % 4 or self.A > 64:
             raise NotImplementedError("%s: attn_dim must be a multiple of 4, at most 64 (got %d)" % (what, self.A))
         self.proj_lin = dec.linear_projection.linear_layer
-        self.proj = (_resid(self.proj_lin.weight), _c(self.proj_lin.bias))
+        self.proj = (contract.resid(self.proj_lin.weight), detached(self.proj_lin.bias))
 
 
 class DecoderPack(_LoopPack):
@@ -351,8 +297,8 @@ class DecoderPack(_LoopPack):
         self.fcs = rnn.speech_prenet_linears(m.prenet)
         self.M = po.linear_project.weight.shape[0]
         self.head, self.ldh = rnn.padded_head(po.linear_project, po.stop_linear)            # [linear_project | stop_linear | zero rows] as one head
-        self.post = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.speech_postnet_stages(po)]
-        self.post_out = rnn.tap_major(po.conv2.conv) + (po.conv2.conv,)
+        self.post = [contract.tap_major(conv) + (conv, bn) for conv, bn in rnn.speech_postnet_stages(po)]
+        self.post_out = contract.tap_major(po.conv2.conv) + (po.conv2.conv,)
 
 
 def _decoder_params(model):
@@ -366,8 +312,8 @@ class TextDecoderPack(_LoopPack):
     def __init__(self, m):
         super().__init__(m, "text_decoder_forward")
         pn, fc = m.prenet, m.postnet.fc1
-        self.emb = _c(pn.embed.weight)
-        self.convs = [rnn.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(pn)]
+        self.emb = detached(pn.embed.weight)
+        self.convs = [contract.tap_major(conv) + (conv, bn) for conv, bn in rnn.text_prenet_stages(pn)]
         E = self.emb.shape[1]
         if E % 4 or 256 % (E // 4) or any(tuple(wp[0].shape[::2]) != (256, cin) or wp[0].shape[1] != 5 for (wp, _, _, _), cin in zip(self.convs, (E, 256, 256))):
             raise NotImplementedError("text_decoder_forward: three 5-tap convs into 256 channels over an embedding whose width / 4 divides 256")
@@ -378,7 +324,7 @@ class TextDecoderPack(_LoopPack):
 
 
 def decoder_pack_of(m, cls=DecoderPack):
-    return rnn.cached_operands(m, rnn.DECODER_TRAIN_SLOT, _decoder_params(m), lambda: cls(m))
+    return contract.cached_operands(m, rnn.DECODER_TRAIN_SLOT, _decoder_params(m), lambda: cls(m))
 
 
 class DecoderTape(Tape):
@@ -427,17 +373,17 @@ def decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     # ---- batched before the loop: the prenet on all fed frames ------------------------------------------------------------------------------
     feed = ops.shift_frames(mel, torch.empty_like(mel)).view(N, M)                          # feed_0 = 0, feed_i = target[:, i-1]
     (w1, b1, _), (w2, b2, _) = P.fcs
-    a1 = _linear_rows(feed, w1, b1)
+    a1 = contract.linear_rows(feed, w1, b1)
     h1 = torch.empty_like(a1)
     ops.leaky_dropout(a1, None, h1, 0.0, p_pre, seed, S_DPRE)
     tape.site("d_prenet_dropout", p_pre, S_DPRE, N, a1.shape[1])
-    pre = _linear_rows(h1, w2, b2, act=1)
+    pre = contract.linear_rows(h1, w2, b2, act=1)
     tape.feed, tape.a1, tape.h1 = feed, a1, h1
     o = _loop_forward(tape, pre, mark)
 
     # ---- batched after the loop: the head, the post-net -----------------------------------------------------------------------------------------
     dev = mel.device
-    head = _linear_rows(o, P.head[0], P.head[1]).view(B, T, P.ldh)
+    head = contract.linear_rows(o, P.head[0], P.head[1]).view(B, T, P.ldh)
     outs = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)                                 # position 0 = the all-zero go frame
     outs[:, 1:].copy_(head[:, :, :M])
     tape.stop = head[:, :, M].contiguous()
@@ -453,7 +399,7 @@ def _postnet_forward(tape, outs, stream0, what):
     [B, T+1, M].  Shared by decoder_forward and speech_generate_train."""
     P, (B, T1, _) = tape.P, outs.shape
     y = _bn_stages_forward(tape, outs, P.post, 4, 2, float(tape.model.postnet.p), stream0, ["post_dropout%d" % k for k in range(4)], what)
-    post = _conv(y.view(B, T1, 256), P.post_out[0], P.post_out[1], 4)
+    post = contract.conv(y.view(B, T1, 256), P.post_out[0], P.post_out[1], 4)
     ops.add_inplace(post, outs)
     return post
 
@@ -465,12 +411,12 @@ def _bn_stages_forward(tape, cur, stages, pad_left, act, p, stream0, names, what
     B, T, _ = cur.shape
     N, dev = B * T, cur.device
     tape.xs, tape.zs = [cur.view(N, -1)], []
-    tape.mean, tape.rstd = _buf(len(stages), 256, dev=dev), _buf(len(stages), 256, dev=dev)
+    tape.mean, tape.rstd = buf(len(stages), 256, dev=dev), buf(len(stages), 256, dev=dev)
     bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
     for k, (wp, bias, _, bn) in enumerate(stages):
-        _check_bn(bn, what)
-        z = _conv(cur, wp, bias, pad_left).view(N, 256)
-        y = _buf(N, 256, dev=dev)
+        contract.check_bn(bn, what)
+        z = contract.conv(cur, wp, bias, pad_left).view(N, 256)
+        y = buf(N, 256, dev=dev)
         ops.bn_fwd(z, bn.weight, bn.bias, y, tape.mean[k], tape.rstd[k], bn.running_mean, bn.running_var, bn_ws, act, drop_p=p, seed=tape.seed,
                    stream_id=stream0 + k, eps=bn.eps, momentum=bn.momentum, num_batches_tracked=bn.num_batches_tracked)
         tape.site(names[k], p, stream0 + k, N, 256)
@@ -479,11 +425,6 @@ def _bn_stages_forward(tape, cur, stages, pad_left, act, p, stream0, names, what
         cur = y.view(B, T, 256)
     rnn.drop_eval_pack(tape.model)
     return y
-
-
-def _check_bn(bn, what):
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise NotImplementedError("%s: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)" % what)
 
 
 def _begin_decoder_tape(what, model, pack_cls, enc_outputs, lens_k, B, T, seed, dev):
@@ -523,8 +464,8 @@ class _TrainCell:
     def __init__(self, tape):
         P, enc, B, Tk = tape.P, tape.enc, tape.B, tape.Tk
         self.P, self.enc, self.lens, self.h0, self.c0 = P, enc, tape.lens, tape.h0, tape.c0
-        self.mem = _linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, P.A)       # memory-side projection, once for all positions
-        self.ga, self.gb = _buf(B, 1024, dev=enc.device), _buf(B, 1024, dev=enc.device)
+        self.mem = contract.linear_rows(enc.view(B * Tk, 512), P.Wmem, None).view(B, Tk, P.A)  # memory-side projection, once for all positions
+        self.ga, self.gb = buf(B, 1024, dev=enc.device), buf(B, 1024, dev=enc.device)
 
     def __call__(self, first, xp0, mask, h0d, q, w_in, w_out, cum_in, cum_out, ctx, h0_in, h0_out, s0, c0_in, s1, c1_in, h1_out):
         """xp0 = W_ih_l0[:, :256] prenet + b_ih; mask / h0d: nn.LSTM's inter-layer dropout factors and the dropped h0_out (None with dropout off);
@@ -553,7 +494,7 @@ def _loop_forward(tape, pre, mark):
     dev = tape.enc.device
     N, lsa = B * T, P.mode == ops.ATTN_LSA
     p_dec = float(model.decoder.p)
-    xp0 = _linear_rows(pre, P.w_ih0_p, P.bias[0]).view(B, T, 1024)
+    xp0 = contract.linear_rows(pre, P.w_ih0_p, P.bias[0]).view(B, T, 1024)
     cell = _TrainCell(tape)
     tape.pre_act, tape.mem = pre, cell.mem
 
@@ -561,13 +502,13 @@ def _loop_forward(tape, pre, mark):
     Tkp = (Tk + 3) // 4 * 4
     W = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev)                                  # W[:, i+1] = w_i; W[:, 0] = 0 is position 0's prev
     CUM = torch.zeros(B, T + 1, Tkp, dtype=_F32, device=dev) if lsa else None               # CUM[:, i] = what position i read
-    HC = _buf(B, T, 768, dev=dev)                                                           # [h1_i | ctx_i]: the projection's input rows
-    H0 = _buf(B, T + 1, 256, dev=dev)                                                       # H0[:, i] = layer 0's h before position i
+    HC = buf(B, T, 768, dev=dev)                                                            # [h1_i | ctx_i]: the projection's input rows
+    H0 = buf(B, T + 1, 256, dev=dev)                                                        # H0[:, i] = layer 0's h before position i
     H0[:, 0].copy_(tape.h0[0])
-    S0, S1 = _buf(B, T, 5, 256, dev=dev), _buf(B, T, 5, 256, dev=dev)
+    S0, S1 = buf(B, T, 5, 256, dev=dev), buf(B, T, 5, 256, dev=dev)
     F1 = _drop_factor(p_dec, seed, S_DDROP, N, 256, dev).view(B, T, 256) if p_dec > 0.0 else None
     tape.site("d_drop0", p_dec, S_DDROP, N, 256)
-    H0d = _buf(B, T, 256, dev=dev) if F1 is not None else None
+    H0d = buf(B, T, 256, dev=dev) if F1 is not None else None
     if mark is not None:
         mark("loop_begin")
     for i in range(T):                                                                      # (index -1 at i = 0: the cell does not read those views)
@@ -579,7 +520,7 @@ def _loop_forward(tape, pre, mark):
     tape.W, tape.CUM, tape.HC, tape.H0, tape.H0d, tape.S0, tape.S1, tape.F1 = W, CUM, HC, H0, H0d, S0, S1, F1
 
     # ---- batched after the loop: projection + tanh + dropout1 ------------------------------------------------------------------------------------
-    tz = ops.tanh_rows(_linear_rows(HC.view(N, 768), P.proj[0], P.proj[1]))
+    tz = ops.tanh_rows(contract.linear_rows(HC.view(N, 768), P.proj[0], P.proj[1]))
     o = tz
     if p_dec > 0.0:
         o = torch.empty_like(tz)
@@ -587,25 +528,6 @@ def _loop_forward(tape, pre, mark):
     tape.site("d_dropout1", p_dec, S_DOUT, N, 256)
     tape.tz, tape.o = tz, o
     return o
-
-
-def _conv_grads(dz2d, x2d, B, T, wpair, conv, pad_left):
-    """Weight, bias and input gradient of one tap-major conv with fp32-level products (the text prenets' and the post-net's backward)."""
-    wp, wr = wpair
-    C, Cin = dz2d.shape[1], x2d.shape[1]
-    dz, dzh, dzr = (t.view(B, T, C) for t in _parts(dz2d))
-    gw = torch.zeros_like(wp)
-    x3, x3res = x2d.view(B, T, Cin), _resid_of(x2d).view(B, T, Cin)
-    ops.conv_taps_wgrad(dzh, x3, gw, pad_left)
-    ops.conv_taps_wgrad(dzr, x3, gw, pad_left)
-    ops.conv_taps_wgrad(dz, x3res, gw, pad_left)
-    conv.weight.grad.add_(gw.permute(0, 2, 1))
-    ops.colsum(dz.view(B * T, C), conv.bias.grad)
-    dx = _buf(B, T, Cin, dev=dz2d.device)
-    ops.conv_taps_dgrad(dzh, wp, dx, pad_left)
-    ops.conv_taps_dgrad(dzr, wp, dx, pad_left, beta=1)
-    ops.conv_taps_dgrad(dz, wr, dx, pad_left, beta=1)
-    return dx.view(B * T, Cin)
 
 
 def _add_over_b(part, grad):
@@ -632,7 +554,7 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     d_pre, d_post = _cot(d_pre, (B, T, M), "d_pre", dev, "decoder_backward"), _cot(d_post, (B, T, M), "d_post", dev, "decoder_backward")
     d_stop = _cot(d_stop, (B, T), "d_stop", dev, "decoder_backward")
     tape.used = True
-    _prepare_grads(_decoder_params(model), accumulate)
+    contract.prepare_grads(_decoder_params(model), accumulate)
     po = model.postnet
     p_pre, p_post = float(model.prenet.p), float(po.p)
 
@@ -641,46 +563,46 @@ def decoder_backward(tape, d_pre=None, d_post=None, d_stop=None, accumulate=Fals
     if d_post is not None:
         dpf = torch.zeros(B, T + 1, M, dtype=_F32, device=dev)
         dpf[:, 1:].copy_(d_post)
-        dy = _conv_grads(dpf.view(N1, M), tape.xs[4], B, T + 1, P.post_out[0], P.post_out[2], 4)
+        dy = contract.conv_grads(dpf.view(N1, M), tape.xs[4], B, T + 1, P.post_out[0], P.post_out[2], 4)
         bn_ws = torch.empty(512, dtype=torch.float64, device=dev)
         for k in (3, 2, 1, 0):
             wpair, _, conv, bn = P.post[k]
-            dz = _buf(N1, 256, dev=dev)
+            dz = buf(N1, 256, dev=dev)
             ops.bn_bwd(dy, tape.zs[k], tape.mean[k], tape.rstd[k], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, bn_ws, 2, drop_p=p_post, seed=seed,
                        stream_id=S_POST + k)
-            dy = _conv_grads(dz, tape.xs[k], B, T + 1, wpair, conv, 4)
+            dy = contract.conv_grads(dz, tape.xs[k], B, T + 1, wpair, conv, 4)
         ops.add_inplace(dpf, dy)                                                            # outputs + postnet(outputs): the residual's share
         d_head[:, :, :M].copy_(dpf[:, 1:])                                                  # (the go frame's gradient is dropped: a constant)
     if d_pre is not None:
         d_head[:, :, :M].add_(d_pre)
     if d_stop is not None:
         d_head[:, :, M].copy_(d_stop)
-    dhp = _parts(d_head.view(N, ldh))
+    dhp = contract.parts(d_head.view(N, ldh))
     gW, gb = torch.zeros(ldh, 256, dtype=_F32, device=dev), torch.zeros(ldh, dtype=_F32, device=dev)
-    _wgrad_rows(dhp, ALL, tape.o, _resid_of(tape.o), gW, (gb,))
+    contract.wgrad_rows(dhp, ALL, tape.o, contract.resid_of(tape.o), gW, (gb,))
     po.linear_project.weight.grad.add_(gW[:M])
     po.linear_project.bias.grad.add_(gb[:M])
     po.stop_linear.weight.grad.add_(gW[M:M + 1])
     po.stop_linear.bias.grad.add_(gb[M:M + 1])
-    d_o = _dgrad_rows(dhp, P.head[0], _buf(N, 256, dev=dev))
+    d_o = contract.dgrad_rows(dhp, P.head[0], buf(N, 256, dev=dev))
     dg0p, d_enc, d_h, d_c = _loop_backward(tape, d_o, mark)
     # the prenet (shared with the encoder)
-    d_p = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev))
+    d_p = contract.dgrad_rows(dg0p, P.w_ih0_p, buf(N, 256, dev=dev))
     (w1, _, fc1), (w2, _, fc2) = P.fcs
     ops.relu_bwd(d_p, tape.pre_act)
-    dpp = _parts(d_p)
-    _wgrad_rows(dpp, ALL, tape.h1, _resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
-    dh1p = _dgrad_rows(dpp, w2, _buf(N, tape.h1.shape[1], dev=dev))
+    dpp = contract.parts(d_p)
+    contract.wgrad_rows(dpp, ALL, tape.h1, contract.resid_of(tape.h1), fc2.weight.grad, (fc2.bias.grad,))
+    dh1p = contract.dgrad_rows(dpp, w2, buf(N, tape.h1.shape[1], dev=dev))
     da1 = torch.empty_like(dh1p)
     ops.leaky_dropout(tape.a1, dh1p, da1, 0.0, p_pre, seed, S_DPRE)
-    _wgrad_rows(_parts(da1), ALL, tape.feed, _resid_of(tape.feed), fc1.weight.grad, (fc1.bias.grad,))
+    contract.wgrad_rows(contract.parts(da1), ALL, tape.feed, contract.resid_of(tape.feed), fc1.weight.grad, (fc1.bias.grad,))
     return d_enc, d_h, d_c
 
 
 def _loop_backward(tape, d_o, mark):
     """Backward of _loop_forward, shared by both decoders: d_o [B*T,256] = the gradient of the head's input.  Writes the gradients of
     model.decoder's parameters (all of W_ih_l0 included: its first 256 columns contract with the prenet rows on the tape).  Returns
-    (dg0p, d_enc_output, d_h, d_c): dg0p = _parts of layer 0's gate gradients [B*T,1024] -- the caller's prenet gradient is
+    (dg0p, d_enc_output, d_h, d_c): dg0p = contract.parts of layer 0's gate gradients [B*T,1024] -- the caller's prenet gradient is
     dg0p . W_ih_l0[:, :256] -- and the three cotangents encoder_backward takes."""
     model, P, B, T, Tk, seed, lens = tape.model, tape.P, tape.B, tape.T, tape.Tk, tape.seed, tape.lens
     A, lsa, N = P.A, P.mode == ops.ATTN_LSA, B * T
@@ -691,23 +613,23 @@ def _loop_backward(tape, d_o, mark):
         d_od = torch.empty_like(d_o)
         ops.leaky_dropout(d_o, d_o, d_od, 1.0, p_dec, seed, S_DOUT)                         # slope 1: the mask and its 1/(1-p) only
         d_o = d_od
-    dzp = _parts(ops.tanh_bwd(d_o, tape.tz))
+    dzp = contract.parts(ops.tanh_bwd(d_o, tape.tz))
     HC2 = tape.HC.view(N, 768)
-    HC2res = _resid_of(HC2)
-    _wgrad_rows(dzp, ALL, HC2, HC2res, P.proj_lin.weight.grad, (P.proj_lin.bias.grad,))
-    DHC = _dgrad_rows(dzp, P.proj[0], _buf(N, 768, dev=dev)).view(B, T, 768)                # [d_h1 | d_ctx] of the projection, all positions
+    HC2res = contract.resid_of(HC2)
+    contract.wgrad_rows(dzp, ALL, HC2, HC2res, P.proj_lin.weight.grad, (P.proj_lin.bias.grad,))
+    DHC = contract.dgrad_rows(dzp, P.proj[0], buf(N, 768, dev=dev)).view(B, T, 768)         # [d_h1 | d_ctx] of the projection, all positions
 
     # ---- the loop, i = T-1 .. 0: 7 launches per position --------------------------------------------------------------------------------------------
     z = lambda *s: torch.zeros(*s, dtype=_F32, device=dev)                                  # noqa: E731
     Tkp = tape.W.shape[2]
     dh0, dh1, dc0, dc1 = z(B, 256), z(B, 256), z(B, 256), z(B, 256)
-    DG0, DG1 = _buf(B, T, 1024, dev=dev), _buf(B, T, 1024, dev=dev)
-    DCTX, DQ = _buf(B, T, 512, dev=dev), _buf(B, T, A, dev=dev)
+    DG0, DG1 = buf(B, T, 1024, dev=dev), buf(B, T, 1024, dev=dev)
+    DCTX, DQ = buf(B, T, 512, dev=dev), buf(B, T, A, dev=dev)
     d_mem, dv_part = z(B, Tk, A), z(B, A)
     dd_part, dcv_part = (z(B, A, 32), z(B, 32, 2, 31)) if lsa else (None, None)
     dprev, dcum = ([z(B, Tkp), z(B, Tkp)], [z(B, Tkp), z(B, Tkp)]) if lsa else ([None, None], [None, None])
     ws = ops.rnn_attn_step_bwd_ws(B, Tk, A, dev)
-    t256, dh_att = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+    t256, dh_att = buf(B, 256, dev=dev), buf(B, 256, dev=dev)
     W, CUM, HC, S0, S1, F1, h0, c0 = tape.W, tape.CUM, tape.HC, tape.S0, tape.S1, tape.F1, tape.h0, tape.c0
     sl = lambda t: t[:, :Tk] if t is not None else None                                     # noqa: E731
     if mark is not None:
@@ -729,31 +651,31 @@ def _loop_backward(tape, d_o, mark):
 
     # ---- batched after the loop: every weight and bias gradient, the prenet, the memory side ---------------------------------------------------------
     r = dec.rnn
-    dg0p, dg1p = _parts(DG0.view(N, 1024)), _parts(DG1.view(N, 1024))
+    dg0p, dg1p = contract.parts(DG0.view(N, 1024)), contract.parts(DG1.view(N, 1024))
     pre = tape.pre_act
-    _wgrad_rows(dg0p, ALL, pre, _resid_of(pre), r.weight_ih_l0.grad[:, :256], (r.bias_ih_l0.grad, r.bias_hh_l0.grad))
-    _wgrad_rows(dg0p, ALL, HC2[:, 256:], HC2res[:, 256:], r.weight_ih_l0.grad[:, 256:])
+    contract.wgrad_rows(dg0p, ALL, pre, contract.resid_of(pre), r.weight_ih_l0.grad[:, :256], (r.bias_ih_l0.grad, r.bias_hh_l0.grad))
+    contract.wgrad_rows(dg0p, ALL, HC2[:, 256:], HC2res[:, 256:], r.weight_ih_l0.grad[:, 256:])
     h0prev = tape.H0[:, :T].contiguous().view(N, 256)
-    _wgrad_rows(dg0p, ALL, h0prev, _resid_of(h0prev), r.weight_hh_l0.grad)
+    contract.wgrad_rows(dg0p, ALL, h0prev, contract.resid_of(h0prev), r.weight_hh_l0.grad)
     x1 = (tape.H0d if F1 is not None else tape.H0[:, 1:].contiguous()).view(N, 256)
-    _wgrad_rows(dg1p, ALL, x1, _resid_of(x1), r.weight_ih_l1.grad, (r.bias_ih_l1.grad, r.bias_hh_l1.grad))
+    contract.wgrad_rows(dg1p, ALL, x1, contract.resid_of(x1), r.weight_ih_l1.grad, (r.bias_ih_l1.grad, r.bias_hh_l1.grad))
     qry = torch.cat([h0[1][:, None, :], HC[:, :T - 1, :256]], 1).contiguous().view(N, 256)  # h1 before each position: W_hh_l1's input and the queries
-    qry_res = _resid_of(qry)
-    _wgrad_rows(dg1p, ALL, qry, qry_res, r.weight_hh_l1.grad)
-    _wgrad_rows(_parts(DQ.view(N, A)), ALL, qry, qry_res, P.q_lin.weight.grad)
+    qry_res = contract.resid_of(qry)
+    contract.wgrad_rows(dg1p, ALL, qry, qry_res, r.weight_hh_l1.grad)
+    contract.wgrad_rows(contract.parts(DQ.view(N, A)), ALL, qry, qry_res, P.q_lin.weight.grad)
     _add_over_b(dv_part, P.v_lin.weight.grad)
     if lsa:
         _add_over_b(dd_part, P.dense_lin.weight.grad)
         _add_over_b(dcv_part, P.conv_mod.weight.grad)
     # the memory side: dW_mem = d_mem^T enc, d_enc = d_mem W_mem + per sequence w_b^T [Tk,T] . d_ctx_b [T,512] (formed once, after the loop)
     enc2 = tape.enc.view(B * Tk, 512)
-    dmp = _parts(d_mem.view(B * Tk, A))
-    _wgrad_rows(dmp, ALL, enc2, _resid_of(enc2), P.mem_lin.weight.grad)
-    d_enc = _dgrad_rows(dmp, P.Wmem, _buf(B * Tk, 512, dev=dev)).view(B, Tk, 512)
-    wparts = _parts(W[:, 1:])
-    dctx_res = _resid_of(DCTX)
+    dmp = contract.parts(d_mem.view(B * Tk, A))
+    contract.wgrad_rows(dmp, ALL, enc2, contract.resid_of(enc2), P.mem_lin.weight.grad)
+    d_enc = contract.dgrad_rows(dmp, P.Wmem, buf(B * Tk, 512, dev=dev)).view(B, Tk, 512)
+    wparts = contract.parts(W[:, 1:])
+    dctx_res = contract.resid_of(DCTX)
     for b in range(B):
-        _wgrad_rows(tuple(t[b] for t in wparts), slice(0, Tk), DCTX[b], dctx_res[b], d_enc[b])
+        contract.wgrad_rows(tuple(t[b] for t in wparts), slice(0, Tk), DCTX[b], dctx_res[b], d_enc[b])
     return dg0p, d_enc, torch.stack([dh0, dh1]), torch.stack([dc0, dc1])
 
 
@@ -846,20 +768,20 @@ def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
     if mark is not None:
         mark("prefix_begin")
     E = P.emb.shape[1]
-    x0 = _buf(R, E, dev=dev)
+    x0 = buf(R, E, dev=dev)
     ops.prefix_embed_fwd(ids, P.emb, tabs, x0, SOS_IDX, drop_p=p_pre, seed=seed, stream_id=S_TEMB)
     tape.site("t_emb_dropout", p_pre, S_TEMB, R, E)
     tape.ids, tape.tabs = ids, tabs
     tape.xs, tape.zs = [x0], []
-    tape.mean, tape.rstd = _buf(3, T, 256, dev=dev), _buf(3, T, 256, dev=dev)
-    varu = _buf(T, 256, dev=dev)
+    tape.mean, tape.rstd = buf(3, T, 256, dev=dev), buf(3, T, 256, dev=dev)
+    varu = buf(T, 256, dev=dev)
     ws = ops.prefix_bn_ws(tabs, 256, dev)
-    pre = _buf(B, T, 256, dev=dev)
+    pre = buf(B, T, 256, dev=dev)
     cur = x0
     for i, (wp, bias, _, bn) in enumerate(P.convs):
-        _check_bn(bn, "text_decoder_forward")
-        z = _conv(cur.view(1, R, -1), wp, bias, 2).view(R, 256)                             # the gaps are every neighbour's zero padding
-        y = _buf(R, 256, dev=dev) if i < 2 else None
+        contract.check_bn(bn, "text_decoder_forward")
+        z = contract.conv(cur.view(1, R, -1), wp, bias, 2).view(R, 256)                     # the gaps are every neighbour's zero padding
+        y = buf(R, 256, dev=dev) if i < 2 else None
         ops.prefix_bn_fwd(z, tabs, bn.weight, bn.bias, tape.mean[i], tape.rstd[i], varu, ws, y=y, p_last=pre if i == 2 else None,
                           running_mean=bn.running_mean, running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked, eps=bn.eps,
                           momentum=bn.momentum, drop_p=p_pre, seed=seed, stream_id=S_TPRE + i)
@@ -881,7 +803,7 @@ def text_decoder_forward(model, target, enc_outputs, lens_k, seed=0, mark=None):
         ops.leaky_dropout(o, None, o2, 1.0, p_post, seed, S_TPOST)
     tape.site("t_post_dropout", p_post, S_TPOST, N, 256)
     tape.o2 = o2
-    tape.head = _linear_rows(o2, P.head[0], P.head[1])                                      # [N, ldh] padded logits: what the loss kernels read
+    tape.head = contract.linear_rows(o2, P.head[0], P.head[1])                              # [N, ldh] padded logits: what the loss kernels read
     tape.logits = tape.head.view(B, T, P.ldh)[:, :, :P.V].contiguous()
     return tape
 
@@ -903,18 +825,18 @@ def text_decoder_backward(tape, d_logits, accumulate=False, mark=None):
     if d_logits is None:
         raise ValueError("text_decoder_backward: d_logits must be a float32 CUDA tensor %s" % ((B, T, V),))
     tape.used = True
-    _prepare_grads(_decoder_params(model), accumulate)
+    contract.prepare_grads(_decoder_params(model), accumulate)
     p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
     fc = model.postnet.fc1
 
     d_head = torch.zeros(B, T, ldh, dtype=_F32, device=dev)
     d_head[:, :, :V].copy_(d_logits)
-    dhp = _parts(d_head.view(N, ldh))
+    dhp = contract.parts(d_head.view(N, ldh))
     gW, gb = torch.zeros(ldh, 256, dtype=_F32, device=dev), torch.zeros(ldh, dtype=_F32, device=dev)
-    _wgrad_rows(dhp, ALL, tape.o2, _resid_of(tape.o2), gW, (gb,))
+    contract.wgrad_rows(dhp, ALL, tape.o2, contract.resid_of(tape.o2), gW, (gb,))
     fc.weight.grad.add_(gW[:V])
     fc.bias.grad.add_(gb[:V])
-    d_o = _dgrad_rows(dhp, P.head[0], _buf(N, 256, dev=dev))
+    d_o = contract.dgrad_rows(dhp, P.head[0], buf(N, 256, dev=dev))
     if p_post > 0.0:
         d_od = torch.empty_like(d_o)
         ops.leaky_dropout(d_o, d_o, d_od, 1.0, p_post, seed, S_TPOST)
@@ -924,16 +846,16 @@ def text_decoder_backward(tape, d_logits, accumulate=False, mark=None):
     # ---- the prefix prenet: d_P sits on each prefix's last row and spreads through the statistics to every row of the prefix -------------------------
     if mark is not None:
         mark("prefix_begin")
-    dy = _dgrad_rows(dg0p, P.w_ih0_p, _buf(N, 256, dev=dev)).view(B, T, 256)
+    dy = contract.dgrad_rows(dg0p, P.w_ih0_p, buf(N, 256, dev=dev)).view(B, T, 256)
     ws = ops.prefix_bn_ws(tabs, 256, dev)
     for i in (2, 1, 0):
         wpair, _, conv, bn = P.convs[i]
-        dz = _buf(R, 256, dev=dev)
+        dz = buf(R, 256, dev=dev)
         ops.prefix_bn_bwd(dy, tape.zs[i], tabs, tape.mean[i], tape.rstd[i], bn.weight, bn.bias, dz, bn.weight.grad, bn.bias.grad, ws, last_only=(i == 2),
                           drop_p=p_pre, seed=seed, stream_id=S_TPRE + i)
-        dy = _conv_grads(dz, tape.xs[i], 1, R, wpair, conv, 2)                              # its gap rows hold the neighbours' spill: nobody reads them
+        dy = contract.conv_grads(dz, tape.xs[i], 1, R, wpair, conv, 2)                      # its gap rows hold the neighbours' spill: nobody reads them
     emb = model.prenet.embed
-    G = _buf(B, T + 1, dy.shape[1], dev=dev)
+    G = buf(B, T + 1, dy.shape[1], dev=dev)
     ops.prefix_embed_bwd(dy, tabs, G, drop_p=p_pre, seed=seed, stream_id=S_TEMB)
     ids_ext = torch.cat([torch.full((B, 1), SOS_IDX, dtype=torch.int64, device=dev), tape.ids], 1).contiguous()
     ops.embed_bwd(ids_ext, G.view(B * (T + 1), -1), emb.weight.grad, T + 1, padding_idx=emb.padding_idx if emb.padding_idx is not None else -1)
@@ -975,14 +897,14 @@ class _GenState:
         z = lambda *s: torch.zeros(*s, dtype=_F32, device=dev)                              # noqa: E731
         self.cell = _TrainCell(tape)
         self.W, self.CUM = z(2, B, Tkp), (z(2, B, Tkp) if self.lsa else None)
-        self.HC, self.H0, self.H0d = z(2, B, 768), z(2, B, 256), _buf(B, 256, dev=dev)
+        self.HC, self.H0, self.H0d = z(2, B, 768), z(2, B, 256), buf(B, 256, dev=dev)
         self.S0, self.S1 = z(2, B, 5, 256), z(2, B, 5, 256)
         self.H0[0].copy_(tape.h0[0])
         W, CUM, HC, H0, S0, S1 = self.W, self.CUM, self.HC, self.H0, self.S0, self.S1
         # where the cell's rows live at even and at odd positions (c = i & 1, p the other half); H0[c] = layer 0's h before position i
         self.halves = [(HC[p, :, :256], W[p, :, :Tk], W[c, :, :Tk], CUM[p, :, :Tk] if self.lsa else None, CUM[c, :, :Tk] if self.lsa else None, HC[c, :, 256:],
                         H0[c], H0[p], S0[c], S0[p, :, 4], S1[c], S1[p, :, 4], HC[c, :, :256]) for c, p in ((0, 1), (1, 0))]
-        self.xp0, self.tz, self.o = _buf(B, 1024, dev=dev), _buf(B, 256, dev=dev), _buf(B, 256, dev=dev)
+        self.xp0, self.tz, self.o = buf(B, 1024, dev=dev), buf(B, 256, dev=dev), buf(B, 256, dev=dev)
         self.p_dec = float(tape.model.decoder.p)
         self.F1 = _drop_factor(self.p_dec, tape.seed, stream_drop, max_len * B, 256, dev).view(max_len, B, 256) if self.p_dec > 0.0 else None
         tape.site("g_drop0", self.p_dec, stream_drop, max_len * B, 256)
@@ -1043,7 +965,7 @@ def text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0):
         raise NotImplementedError("%s: an embedding width that is a multiple of 64, at most 256 (got %d)" % (what, E))
     bns = [bn for _, _, _, bn in P.convs]
     for bn in bns:
-        _check_bn(bn, what)
+        contract.check_bn(bn, what)
     p_pre, p_post = float(model.prenet.p), float(model.postnet.p)
     st = _GenState(tape, max_len, S_GDROP)
     rows = B * max_len
@@ -1053,9 +975,9 @@ def text_generate_train(model, enc_outputs, lens_k, max_len=300, seed=0):
     tape.site("g_dropout_out", st.p_dec, S_GOUT, rows, 256)
     tape.site("g_post_dropout", p_post, S_GPOST, rows, 256)
     tokens = torch.zeros(B, max_len, dtype=torch.int64, device=dev)
-    zs = [_buf(rows, 256, dev=dev) for _ in range(3)]
+    zs = [buf(rows, 256, dev=dev) for _ in range(3)]
     parts = torch.empty(3 * ops.prefix_gen_tiles(B, max_len) * 512, dtype=torch.float64, device=dev)
-    pre, o2, logits = _buf(B, 256, dev=dev), _buf(B, 256, dev=dev), _buf(B, P.ldh, dev=dev)
+    pre, o2, logits = buf(B, 256, dev=dev), buf(B, 256, dev=dev), buf(B, P.ldh, dev=dev)
     Ws = [(wp[0], bias) for wp, bias, _, _ in P.convs]
 
     def one(i):
@@ -1103,8 +1025,8 @@ def speech_generate_train(model, enc_outputs, lens_k, max_len=815, seed=0):
     tape.site("g_dropout_out", st.p_dec, S_SGOUT, rows, 256)
     frames = torch.zeros(B, max_len + 1, M, dtype=_F32, device=dev)                         # position 0 = the all-zero go frame
     stops = torch.zeros(B, max_len, dtype=_F32, device=dev)
-    a1, h1, pre = _buf(B, w1[0].shape[0], dev=dev), _buf(B, w1[0].shape[0], dev=dev), _buf(B, 256, dev=dev)
-    head = _buf(B, P.ldh, dev=dev)
+    a1, h1, pre = buf(B, w1[0].shape[0], dev=dev), buf(B, w1[0].shape[0], dev=dev), buf(B, 256, dev=dev)
+    head = buf(B, P.ldh, dev=dev)
 
     def one(i):
         ops.rnn_linear(frames[:, i], w1[0], b1, a1)

@@ -14,7 +14,7 @@ after it starts from zero.
 Where what lives.  The discriminator keeps living in the model's FlatStore (UNAST._store() of an RNN model covers the discriminator alone:
 its kernels address its LSTM weights as spans of that buffer); the optimizer takes the store's 'disc' region as one more segment next to
 its own two -- flat parameter and gradient buffers for text_m and for speech_m with p.data / p.grad as views (flat_adam.adopt;
-train_rnn._prepare_grads keeps such a .grad in place).  Segments, launch sequence and (de)serialisation are unast_amd.flat_adam's, shared with
+contract.prepare_grads keeps such a .grad in place).  Segments, launch sequence and (de)serialisation are unast_amd.flat_adam's, shared with
 the transformer's and the vocoder's optimizers; this module decides which segments step.  A segment whose gradients were not produced since
 the last zero_grad is skipped entirely -- no decay, no moment update, no step count, no share in the clip norm: torch.optim's
 `grad is None`.  'Produced' is tracked on the host (model._rnn_touched, FlatStore.touched).

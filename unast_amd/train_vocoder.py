@@ -4,12 +4,15 @@ backward, clip, Adam(W), schedule) without its dataset, TensorBoard and file han
 `vocoder_step` is the explicit entry point of the train-mode forward and backward; `Vocoder.forward` stays the eval forward.  BatchNorm
 runs on batch statistics over all B*T rows (padded rows included: the reference does not mask) and updates its running statistics as
 nn.BatchNorm1d does.  The backward's discrete decisions -- ReLU gates, the max pool's choice, the L1 sign -- are read from what the
-forward stored, never recomputed.  Everything is enqueued on the current stream; the loss stays on the device.  DESIGN 5g.
+forward stored, never recomputed.  Every forward contraction is one of unast_amd.contract's three-launch forms (linear_rows, conv) over
+weight pairs derived per call, just ahead of each stage; the backward keeps one launch per gradient contraction (_wgrad, ops.linear_dgrad,
+ops.conv_taps_wgrad / _dgrad).  Everything is enqueued on the current stream; the loss stays on the device.  DESIGN 5g, 5t.
 """
 import torch
 
-from . import flat_adam, ops
-from .vocoder import Vocoder
+from . import contract, flat_adam, ops
+from .contract import buf
+from .vocoder import Vocoder, gru_operands, highway_operands
 
 _F32 = torch.float32
 
@@ -28,33 +31,6 @@ def _loss_flag(loss_type):
     if loss_type not in ("l1", "l2"):
         raise ValueError("loss_type must be 'l1' or 'l2' (src/train_vocoder.py:58-61), got %r" % (loss_type,))
     return loss_type == "l2"
-
-
-def _grads(model):
-    """Dense zeroed .grad of every parameter, in the reference's shapes (kept when they already are: FlatAdamW's views stay in place)."""
-    gs = []
-    for p in model.parameters():
-        g = p.grad
-        if g is None or not g.is_contiguous() or g.dtype is not _F32 or g.device != p.device or g.data_ptr() % 16:
-            g = p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        gs.append(g)
-    torch._foreach_zero_(gs)
-
-
-def _gru_operands(gru, layer):
-    """One layer's operands as vocoder._Pack lays them out: weight_ih of both directions [768,256], its bias with b_hr, b_hz added,
-    weight_hh [2,384,128], b_hn [2,128]."""
-    H = gru.hidden_size
-    w_ih, b_x, w_hh, b_hn = [], [], [], []
-    for sfx in ("_l%d" % layer, "_l%d_reverse" % layer):
-        b_ih, b_hh = getattr(gru, "bias_ih" + sfx), getattr(gru, "bias_hh" + sfx)
-        w_ih.append(getattr(gru, "weight_ih" + sfx))
-        w_hh.append(getattr(gru, "weight_hh" + sfx))
-        bx = b_ih.clone()
-        bx[:2 * H] += b_hh[:2 * H]
-        b_x.append(bx)
-        b_hn.append(b_hh[2 * H:])
-    return torch.cat(w_ih).contiguous(), torch.cat(b_x).contiguous(), torch.stack(w_hh).contiguous(), torch.stack(b_hn).contiguous()
 
 
 def _wgrad(dy2d, x2d, dW, db):
@@ -85,11 +61,7 @@ def vocoder_step(model, mel, mag, loss_type="l1", taps=None):
     dev = mel.device
     bns = list(c.batchnorm_list) + [c.batchnorm_proj_1, c.batchnorm_proj_2]
     for bn in bns:
-        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-            raise NotImplementedError("vocoder_step: BatchNorm1d with affine parameters, running statistics and a fixed momentum (the reference's)")
-
-    def buf(*shape):
-        return torch.empty(*shape, dtype=_F32, device=dev)
+        contract.check_bn(bn, "vocoder_step")
 
     def bn_fwd(i, z2d, y2d, act):
         bn = bns[i]
@@ -100,101 +72,77 @@ def vocoder_step(model, mel, mag, loss_type="l1", taps=None):
         bn = bns[i]
         ops.bn_bwd(dy2d, z2d, mean[i], rstd[i], bn.weight, bn.bias, dz2d, bn.weight.grad, bn.bias.grad, bn_ws, 0)      # (act 0: dy arrives gated)
 
-    def conv_fwd(x3d, wp, wr, bias, z3d, pad_left):
-        """z = conv(x, W) + bias with fp32-level products: the three-term split-bf16 form drops x_lo W_lo and what lies below 2^-17 of
-        either operand, and 16 chained stages of that put the deepest stages' gradients at 20 x an fp32 step's error.  With
-        x = hi + rest (hi in bf16 exactly) and W = W_hi + W_lo + wr, conv(hi, W) + conv(rest, W) + conv(x, wr) holds every product but
-        the ones of order 2^-26."""
-        ops.split_parts(x3d if x3d.is_contiguous() else x3d.contiguous(), hi=xh[:x3d.numel()], rest=xr[:x3d.numel()])
-        h3, r3 = xh[:x3d.numel()].view(x3d.shape), xr[:x3d.numel()].view(x3d.shape)
-        ops.conv_taps_fwd(h3, wp, bias, za.view(z3d.shape), pad_left)
-        ops.conv_taps_fwd(r3, wp, None, zb.view(z3d.shape), pad_left, R=za)
-        ops.conv_taps_fwd(x3d, wr, None, z3d, pad_left, R=zb)
+    def work(x, z):
+        """The step's scratch as the four temporaries of one forward contraction with input x and output z."""
+        return tuple(t[:like.numel()].view(like.shape) for t, like in zip(scratch, (x, x, z, z)))
 
-    def lin_fwd(x2d, w, bias, out, n_out):
-        """out[:, :n_out] = x2d w^T + bias with the same three launches (the linear layers feed the same chains)."""
-        k, ldc = x2d.shape[1], out.stride(0)
-        wr = torch.empty_like(w)
-        ops.split_parts(w, resid=wr)
-        ops.split_parts(x2d, hi=xh[:x2d.numel()], rest=xr[:x2d.numel()])
-        t1, t2 = torch.empty_like(out), torch.empty_like(out)
-        ops.gemm(ops.OP_KC, ops.OP_KC, xh[:x2d.numel()].view(N, k), k, w, k, t1, ldc, N, n_out, k, bias=bias)
-        ops.gemm(ops.OP_KC, ops.OP_KC, xr[:x2d.numel()].view(N, k), k, w, k, t2, ldc, N, n_out, k, R=t1, ldr=ldc)
-        ops.gemm(ops.OP_KC, ops.OP_KC, x2d, k, wr, k, out, ldc, N, n_out, k, R=t2, ldr=ldc)
-
-    def tap_major(conv):
-        wp = conv.weight.permute(0, 2, 1).contiguous()      # tap-major [Cout,k,Cin]
-        wr = torch.empty_like(wp)
-        ops.split_parts(wp, resid=wr)
-        return wp, wr
-
-    _grads(model)
+    contract.prepare_grads(model.parameters(), False)
     model.__dict__.pop("_vocoder_pack", None)             # the running statistics move under the cached eval operands (kernel writes)
-    mean, rstd = buf(K + 2, C), buf(K + 2, C)
+    mean, rstd = buf(K + 2, C, dev=dev), buf(K + 2, C, dev=dev)
     bn_ws = torch.empty(2 * C, dtype=torch.float64, device=dev)
-    # ---- forward ---------------------------------------------------------------------------------------------------------------------
+    # ---- forward: each contraction's weight pair (contract.resid / tap_major, the extractors of unast_amd.vocoder) is derived per call -- FlatAdamW
+    # moves the parameters behind the version counters, a cache would go stale every step -- and just ahead of its stage: these small launches
+    # then queue behind the stage before, where at the top of the step the GPU would wait for the host through all of them -----------------------
     x2 = mel.contiguous().view(N, M)
     mag2 = mag.contiguous().view(N, F_)
-    pre = model.pre_projection.conv
-    pre_w = pre.weight[:, :, 0].contiguous()
-    x0 = buf(N, C)
-    xh, xr, za, zb = buf(N * K * C), buf(N * K * C), buf(N, C), buf(N, C)       # operand parts and partial sums of conv_fwd / lin_fwd
-    lin_fwd(x2, pre_w, pre.bias, x0, C)
-    zs, ys = buf(K, N, C), buf(K, N, C)                    # bank: conv outputs (BatchNorm inputs) and post-ReLU stage outputs
-    pooled = buf(B, T, K * C)
-    bank_w = []
+    pre, post = model.pre_projection.conv, model.post_projection.conv
+    x0 = buf(N, C, dev=dev)
+    scratch = [buf(N * K * C, dev=dev), buf(N * K * C, dev=dev), buf(N * max(ld, 3 * C), dev=dev), buf(N * max(ld, 3 * C), dev=dev)]  # operand parts and partial sums (work)
+    contract.linear_rows(x2, contract.resid(pre.weight[:, :, 0]), pre.bias, out=x0, work=work(x2, x0))
+    zs, ys = buf(K, N, C, dev=dev), buf(K, N, C, dev=dev)  # bank: conv outputs (BatchNorm inputs) and post-ReLU stage outputs
+    pooled = buf(B, T, K * C, dev=dev)
+    bank_w = []                                             # the weights alone: what the backward's single launches read
     src = x0.view(B, T, C)
     for k in range(1, K + 1):                               # a CHAIN: stage k reads stage k-1 (src/module.py:605-607)
-        conv = c.convbank_list[k - 1]
-        wp, wr = tap_major(conv)
-        bank_w.append(wp)
-        conv_fwd(src, wp, wr, conv.bias, zs[k - 1].view(B, T, C), k // 2)
+        wp, bias = contract.tap_major(c.convbank_list[k - 1])
+        bank_w.append(wp[0])
+        z = zs[k - 1].view(B, T, C)
+        contract.conv(src, wp, bias, k // 2, out=z, work=work(src, z))
         bn_fwd(k - 1, zs[k - 1], ys[k - 1], 1)
         src = ys[k - 1].view(B, T, C)
         ops.maxpool_prev(src, pooled[:, :, (k - 1) * C:k * C])
-    (w1, w1r), (w2, w2r) = tap_major(c.conv_projection_1), tap_major(c.conv_projection_2)
-    z1, p1, z2 = buf(N, C), buf(N, C), buf(N, C)
-    conv_fwd(pooled, w1, w1r, c.conv_projection_1.bias, z1.view(B, T, C), 1)
+    (w1p, b1), (w2p, b2) = contract.tap_major(c.conv_projection_1), contract.tap_major(c.conv_projection_2)
+    w1, w2 = w1p[0], w2p[0]
+    z1, p1, z2 = buf(N, C, dev=dev), buf(N, C, dev=dev), buf(N, C, dev=dev)
+    contract.conv(pooled, w1p, b1, 1, out=z1.view(B, T, C), work=work(pooled, z1.view(B, T, C)))
     bn_fwd(K, z1, p1, 1)
-    conv_fwd(p1.view(B, T, C), w2, w2r, c.conv_projection_2.bias, z2.view(B, T, C), 1)
-    hx = buf(5, N, C)                                       # highway inputs; hx[4] is its output
+    contract.conv(p1.view(B, T, C), w2p, b2, 1, out=z2.view(B, T, C), work=work(p1.view(B, T, C), z2.view(B, T, C)))
+    hx = buf(5, N, C, dev=dev)                              # highway inputs; hx[4] is its output
     bn_fwd(K + 1, z2, hx[0], 0)
     ops.add_inplace(hx[0], x0)                              # residual (src/module.py:619)
-    hts = buf(4, N, 2 * C)
+    hts = buf(4, N, 2 * C, dev=dev)
     hw_w = []
-    for i, (l, g) in enumerate(zip(c.highway.linears, c.highway.gates)):
-        w = torch.cat([l.linear_layer.weight, g.linear_layer.weight]).contiguous()
-        b = torch.cat([l.linear_layer.bias, g.linear_layer.bias]).contiguous()
+    for i, (w, b) in enumerate(highway_operands(c.highway)):
         hw_w.append(w)
-        lin_fwd(hx[i], w, b, hts[i], 2 * C)
+        contract.linear_rows(hx[i], contract.resid(w), b, out=hts[i], work=work(hx[i], hts[i]))
         ops.highway_combine(hts[i], hx[i], hx[i + 1])
-    gy = buf(2, B, T, C)                                    # GRU layer outputs
-    saved = buf(2, B, T, 2, 2 * C)
-    gru_w = []
-    xproj = buf(B, T, 3 * C)
+    gy = buf(2, B, T, C, dev=dev)                           # GRU layer outputs
+    saved = buf(2, B, T, 2, 2 * C, dev=dev)
+    xproj = buf(B, T, 3 * C, dev=dev)
     gin = hx[4]
+    gru_w = []
     for layer in range(2):
-        w_ih, b_x, w_hh, b_hn = _gru_operands(c.gru, layer)
+        w_ih, b_x, w_hh, b_hn = gru_operands(c.gru, layer)
         gru_w.append((w_ih, w_hh))
-        lin_fwd(gin, w_ih, b_x, xproj.view(N, 3 * C), 3 * C)
+        contract.linear_rows(gin, contract.resid(w_ih), b_x, out=xproj.view(N, 3 * C), work=work(gin, xproj.view(N, 3 * C)))
         ops.gru_fwd_train(xproj, w_hh, b_hn, gy[layer], saved[layer])
         gin = gy[layer].view(N, C)
-    post = model.post_projection.conv
-    post_w = post.weight[:, :, 0].contiguous()
-    out = buf(N, ld)
-    lin_fwd(gin, post_w, post.bias, out, F_)
+    out = buf(N, ld, dev=dev)
+    post_w = contract.resid(post.weight[:, :, 0])
+    contract.linear_rows(gin, post_w, post.bias, out=out, work=work(gin, out))
+    del scratch[:]                                          # (the partial sums are as wide as the prediction: not kept through the backward)
     # ---- loss (src/train_vocoder.py:91) ----------------------------------------------------------------------------------------------
     loss = torch.zeros((), dtype=torch.float64, device=dev)
-    dout = buf(N, ld)
+    dout = buf(N, ld, dev=dev)
     ops.sum_loss(out[:, :F_], mag2, dout[:, :F_], l2, loss)
     if taps is not None:
         taps.update(bank=ys.view(K, B, T, C).permute(1, 2, 0, 3).reshape(B, T, K * C), proj1=p1.view(B, T, C).clone(),
                     highway_pre=[hts[i].clone() for i in range(4)], mag_pred=out.view(B, T, ld)[:, :, :F_])
     # ---- backward (loss.backward(), src/train_vocoder.py:94) -------------------------------------------------------------------------
     _wgrad(dout[:, :F_], gin, post.weight.grad.view(F_, C), post.bias.grad)
-    dg = buf(N, C)
-    ops.linear_dgrad(dout[:, :F_], post_w, dg)
-    dxg, dhn, hs = buf(B, T, 2, 3 * C // 2), buf(B, T, 2, C // 2), buf(B, T, C)
+    dg = buf(N, C, dev=dev)
+    ops.linear_dgrad(dout[:, :F_], post_w[0], dg)
+    dxg, dhn, hs = buf(B, T, 2, 3 * C // 2, dev=dev), buf(B, T, 2, C // 2, dev=dev), buf(B, T, C, dev=dev)
     H = C // 2
     for layer in (1, 0):
         w_ih, w_hh = gru_w[layer]
@@ -214,7 +162,7 @@ def vocoder_step(model, mel, mag, loss_type="l1", taps=None):
             _wgrad(dh2[:, H * d:H * (d + 1)], hs2[:, H * d:H * (d + 1)], g_whh[2 * H:], g_bhh[2 * H:])
             g_bhh[:2 * H].copy_(g_bih[:2 * H])              # b_hr, b_hz only ever appear summed with b_ir, b_iz
         ops.linear_dgrad(dx2, w_ih, dg)
-    dpre = buf(N, 2 * C)
+    dpre = buf(N, 2 * C, dev=dev)
     for i in (3, 2, 1, 0):
         ops.highway_combine_bwd(dg, hts[i], hx[i], dpre, dg)
         l, g = c.highway.linears[i].linear_layer, c.highway.gates[i].linear_layer
@@ -222,7 +170,7 @@ def vocoder_step(model, mel, mag, loss_type="l1", taps=None):
         _wgrad(dpre[:, C:], hx[i], g.weight.grad, g.bias.grad)
         ops.linear_dgrad(dpre, hw_w[i], dg, beta=1)
     # dg = gradient of (BN2(conv2(p1)) + x0): it flows into the projection chain and, as the residual, into x0
-    dz, dz_next, dy = buf(N, C), buf(N, C), buf(N, C)
+    dz, dz_next, dy = buf(N, C, dev=dev), buf(N, C, dev=dev), buf(N, C, dev=dev)
     bn_bwd(K + 1, dg, z2, dz)
     gw2 = torch.zeros_like(w2)
     ops.conv_taps_wgrad(dz.view(B, T, C), p1.view(B, T, C), gw2, 1, db=c.conv_projection_2.bias.grad)
@@ -233,7 +181,7 @@ def vocoder_step(model, mel, mag, loss_type="l1", taps=None):
     gw1 = torch.zeros_like(w1)
     ops.conv_taps_wgrad(dz.view(B, T, C), pooled, gw1, 1, db=c.conv_projection_1.bias.grad)
     c.conv_projection_1.weight.grad.copy_(gw1.permute(0, 2, 1))
-    dpooled = buf(B, T, K * C)
+    dpooled = buf(B, T, K * C, dev=dev)
     ops.conv_taps_dgrad(dz.view(B, T, C), w1, dpooled, 1)
     for k in range(K, 0, -1):
         yk = ys[k - 1].view(B, T, C)

@@ -15,7 +15,7 @@ forward's output as it is, padded rows included.
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import contract, ops
 from .module import Linear, _no_forward
 
 _F32 = torch.float32
@@ -66,13 +66,26 @@ class CBHG(nn.Module):
     forward = _no_forward
 
 
-def _fold_bn(conv, bn):
-    """Tap-major weights and bias of conv followed by eval BatchNorm: BN(Wx + b) = (s W) x + (b - mean) s + beta, s = gamma / sqrt(var + eps).
-    Formed in fp64 and rounded once."""
-    s = bn.weight.double() * torch.rsqrt(bn.running_var.double() + bn.eps)
-    w = (conv.weight.double() * s[:, None, None]).permute(0, 2, 1).contiguous().to(_F32)
-    b = ((conv.bias.double() - bn.running_mean.double()) * s + bn.bias.double()).to(_F32)
-    return w, b
+def highway_operands(highway):
+    """Each highway layer's [linears.i | gates.i] as one (weight [2C, C], bias [2C])."""
+    return [(torch.cat([l.linear_layer.weight, g.linear_layer.weight]).contiguous(),
+             torch.cat([l.linear_layer.bias, g.linear_layer.bias]).contiguous()) for l, g in zip(highway.linears, highway.gates)]
+
+
+def gru_operands(gru, layer):
+    """One layer's operands as the GRU kernels read them: weight_ih of both directions [6H, In], its bias with b_hr, b_hz added, weight_hh
+    [2, 3H, H], b_hn [2, H]."""
+    H = gru.hidden_size
+    w_ih, b_x, w_hh, b_hn = [], [], [], []
+    for sfx in ("_l%d" % layer, "_l%d_reverse" % layer):
+        b_ih, b_hh = getattr(gru, "bias_ih" + sfx), getattr(gru, "bias_hh" + sfx)
+        w_ih.append(getattr(gru, "weight_ih" + sfx))
+        w_hh.append(getattr(gru, "weight_hh" + sfx))
+        bx = b_ih.clone()
+        bx[:2 * H] += b_hh[:2 * H]              # b_hr, b_hz only ever appear summed with b_ir, b_iz; b_hn sits inside r * (.)
+        b_x.append(bx)
+        b_hn.append(b_hh[2 * H:])
+    return torch.cat(w_ih).contiguous(), torch.cat(b_x).contiguous(), torch.stack(w_hh).contiguous(), torch.stack(b_hn).contiguous()
 
 
 class _Pack:
@@ -83,26 +96,11 @@ class _Pack:
         with torch.no_grad():
             self.pre_w = m.pre_projection.conv.weight[:, :, 0].contiguous()
             self.pre_b = m.pre_projection.conv.bias.detach()
-            self.bank = [_fold_bn(conv, bn) for conv, bn in zip(c.convbank_list, c.batchnorm_list)]
-            self.proj1 = _fold_bn(c.conv_projection_1, c.batchnorm_proj_1)
-            self.proj2 = _fold_bn(c.conv_projection_2, c.batchnorm_proj_2)
-            self.highway = [(torch.cat([l.linear_layer.weight, g.linear_layer.weight]).contiguous(),
-                             torch.cat([l.linear_layer.bias, g.linear_layer.bias]).contiguous())
-                            for l, g in zip(c.highway.linears, c.highway.gates)]
-            self.gru = []
-            H = c.gru.hidden_size
-            for layer in range(c.gru.num_layers):
-                w_ih, b_x, w_hh, b_hn = [], [], [], []
-                for sfx in ("_l%d" % layer, "_l%d_reverse" % layer):
-                    b_ih, b_hh = getattr(c.gru, "bias_ih" + sfx), getattr(c.gru, "bias_hh" + sfx)
-                    w_ih.append(getattr(c.gru, "weight_ih" + sfx))
-                    w_hh.append(getattr(c.gru, "weight_hh" + sfx))
-                    bx = b_ih.clone()
-                    bx[:2 * H] += b_hh[:2 * H]              # b_hr, b_hz only ever appear summed with b_ir, b_iz; b_hn sits inside r * (.)
-                    b_x.append(bx)
-                    b_hn.append(b_hh[2 * H:])
-                self.gru.append((torch.cat(w_ih).contiguous(), torch.cat(b_x).contiguous(), torch.stack(w_hh).contiguous(),
-                                 torch.stack(b_hn).contiguous()))
+            self.bank = [contract.fold_bn(conv, bn) for conv, bn in zip(c.convbank_list, c.batchnorm_list)]
+            self.proj1 = contract.fold_bn(c.conv_projection_1, c.batchnorm_proj_1)
+            self.proj2 = contract.fold_bn(c.conv_projection_2, c.batchnorm_proj_2)
+            self.highway = highway_operands(c.highway)
+            self.gru = [gru_operands(c.gru, layer) for layer in range(c.gru.num_layers)]
             self.post_w = m.post_projection.conv.weight[:, :, 0].contiguous()
             self.post_b = m.post_projection.conv.bias.detach()
 
@@ -120,17 +118,7 @@ class Vocoder(nn.Module):
         self.post_projection = _Conv1(hidden_size, self.num_bins)
 
     def _pack(self):
-        ver = 0
-        dev = None
-        for t in list(self.parameters()) + list(self.buffers()):
-            ver += t._version
-            dev = t.device
-        key = (ver, dev)
-        cached = self.__dict__.get("_vocoder_pack")
-        if cached is None or cached[0] != key:
-            cached = (key, _Pack(self))
-            self.__dict__["_vocoder_pack"] = cached
-        return cached[1]
+        return contract.cached_operands(self, "_vocoder_pack", list(self.parameters()) + list(self.buffers()), lambda: _Pack(self))
 
     def forward(self, mel):
         return self._run(mel, None)
